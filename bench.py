@@ -1,7 +1,15 @@
 """Headline benchmark: GB/s encode+decode on a 1 GiB byte stream per MI355X, % HBM roofline.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--cfg C2] [--nary 2] [--size BYTES]
+                    [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...          (driver launches N>1 so)
+
+A plain run does what the headline figure needs and no more: it sets up, warms up, times the
+K steps, writes the outputs of the last timed step when --dump-outputs is given, and prints
+the result line (metric, value, ms_per_step, the configuration). --full adds everything else
+described below to that line: the one-context step time, the encode / decode split, the
+per-kernel times and rooflines, the copy probe, the round-trip check, the gather at N > 1
+and the CPU baseline.
 
 Workload (BASELINE.json metric / configs[1] generator at the metric's 1 GiB): a 1 GiB
 enwik-like synthetic byte stream per GPU, binary (n=2) Huffman. One step = the whole
@@ -11,8 +19,12 @@ codec on that stream, inputs resident in HBM:
              rank's global bit offset (+ sync index)
     decode = parallel decode of the rank's shard back to bytes
 value = total uncompressed bytes of all ranks / step time (GB/s, 1e9), "scaling": "weak".
-The round trip is verified (decoded == input) after the timed region.
 
+--dump-outputs DIR: what the last timed step returned to its caller (payload bytes and bit
+count, sync index, decoded bytes) as DIR/<name>.npy (dump_outputs). The inputs are seeded, so
+two builds run with the same arguments can be compared file by file.
+
+--full: the round trip is verified (decoded == input) after the timed region.
 roofline: dominant kernel, algorithmic bytes per launch / its mean HIP-event duration on
 the codec's stream, against 8.0 TB/s. cpu_baseline: the oracle (single-threaded C
 restatement) on a bounded sample of the same stream, rank 0, N=1 only.
@@ -45,6 +57,13 @@ def parse():
                     help="untimed steps before the W warmup steps: the GPU reaches its steady clocks "
                          "only after ~20-30 ms of load (tools/step_probe.py, profiles/r3w_step_probe.log: "
                          "after 5 warmup steps the first timed steps ran 1.15 -> 1.03 ms, steady 1.02)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check everything beside the headline figure: "
+                         "the one-context step time, the encode / decode split, per-kernel times and rooflines, "
+                         "the copy probe, the round trip, the gather (N > 1) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (payload, bit count, sync index, decoded "
+                         "bytes) as DIR/<name>.npy; arrays above 2 Mi elements as a fixed seeded sample + block sums")
     ap.add_argument("--cfg", default="C2")
     ap.add_argument("--frontend", action="store_true",
                     help="C5 pipeline: small_compression.c front-end, then n-ary Huffman (dist.ShardedSmall)")
@@ -127,6 +146,22 @@ def main():
     _phase(rank, "warmup done")
     ms_step = timed_steps(lanes, a.steps, threaded, world, dev)
     _phase(rank, "timed steps done")
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, huffman_outputs(lanes[(a.steps - 1) % len(lanes)], world), rank, world)
+    res = headline(a, world, n, ms_step, lanes)
+    res["metric"] = METRIC
+    res["config"] = {"workload": f"{a.cfg} {CFG_TEXT.get(a.cfg, a.cfg)}, {n >> 20} MiB per GPU, "
+                                 + ("small front-end + " if a.frontend else "")
+                                 + f"n={a.nary} Huffman encode+decode"
+                                 + (" (configs[1] generator at the metric's 1 GiB)" if a.cfg == "C2" else ""),
+                     "frontend": bool(a.frontend), "fused": bool(a.frontend and getattr(state["s"], "fused", False)),
+                     "bytes_per_gpu": n, "n_ary": a.nary, "sync_syms": S,
+                     "parallelism": f"shard{world}" if world > 1 else "single"}
+    if not a.full:
+        return finish(res, rank, world)
+    if a.dump_outputs:   # the dump broke the run of steps: warm up again before the measurements below
+        run_steps(lanes, a.warmup, threaded)
+        torch.cuda.synchronize()
     ms_serial = timed_steps(lanes[:1], a.steps, False, world, dev) if len(lanes) > 1 else ms_step
     _phase(rank, "serial steps done")
     torch.cuda.set_stream(lane0.stream)   # the rest runs on lane 0 (its codec's stream)
@@ -219,31 +254,8 @@ def main():
     enc_alg = n + payload + sync_bytes   # the pipeline's input (C5: before the front-end) + its output
     enc_frac = enc_alg / (enc_ms * 1e-3) / HBM_PEAK
     dec_frac = enc_alg / (dec_ms * 1e-3) / HBM_PEAK
-    value = world * n / (ms_step * 1e-3) / 1e9
-    res = {
-        "metric": METRIC,
-        "value": round(value, 2),
-        "unit": "GB/s",
-        "n_gpus": world,
-        "steps": a.steps,
-        "warmup": a.warmup,
-        "prewarm": a.prewarm,
-        "ms_per_step": round(ms_step, 4),
-        "in_flight": len(lanes),
-        "in_flight_inputs": "distinct",
+    res.update({
         "ms_per_step_serial": round(ms_serial, 4),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "u8",
-        "data": "synthetic",
-        "config": {"workload": f"{a.cfg} {CFG_TEXT.get(a.cfg, a.cfg)}, {n >> 20} MiB per GPU, "
-                               + ("small front-end + " if a.frontend else "")
-                               + f"n={a.nary} Huffman encode+decode"
-                               + (" (configs[1] generator at the metric's 1 GiB)" if a.cfg == "C2" else ""),
-                   "frontend": bool(a.frontend), "fused": bool(a.frontend and getattr(state["s"], "fused", False)),
-                   "bytes_per_gpu": n, "n_ary": a.nary, "sync_syms": S,
-                   "parallelism": f"shard{world}" if world > 1 else "single"},
         "roofline": {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 1), "peak": HBM_PEAK / 1e9,
                      "unit": "GB/s", "frac": round(achieved * 1e9 / HBM_PEAK, 4), "traffic": traffic,
                      "traffic_source": traffic_src,
@@ -268,17 +280,93 @@ def main():
         "ratio": round(payload / n, 4),
         "kernels": kernels,
         "roundtrip_ok": ok,
-    }
+    })
     if world > 1:
         res["table_mode"] = a.table_mode
         if gather is not None:
             res["gather"] = gather
     if rank == 0 and world == 1 and not a.no_cpu:
         res["cpu_baseline"] = cpu_baseline(x, a)
+    finish(res, rank, world)
+
+
+def headline(a, world, n, ms_step, lanes):
+    """The result line of a plain run (the caller adds its metric and config); --full adds to it."""
+    return {
+        "metric": None,
+        "value": round(world * n / (ms_step * 1e-3) / 1e9, 2),
+        "unit": "GB/s",
+        "n_gpus": world,
+        "steps": a.steps,
+        "warmup": a.warmup,
+        "prewarm": a.prewarm,
+        "ms_per_step": round(ms_step, 4),
+        "in_flight": len(lanes),
+        "in_flight_inputs": "distinct",
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "u8",
+        "data": "synthetic",
+        "full": bool(a.full),
+    }
+
+
+def finish(res, rank, world):
     if rank == 0:
         print(json.dumps(res), flush=True)
     if world > 1:
         dist.destroy_process_group()
+
+
+DUMP_CAP = 1 << 21     # --dump-outputs: arrays up to this many elements are written whole
+DUMP_BLOCK = 1 << 16   # larger ones: a sample of DUMP_CAP elements + the sums of blocks of this many
+DUMP_LIMIT = 64 * 10**6
+
+
+def dump_outputs(d, arrays, rank, world):
+    """--dump-outputs: the named device arrays as d/<name>.npy (at N > 1: <name>.rank<r>.npy),
+    values exact in float32 (1- and 2-byte elements) or float64. An array above DUMP_CAP
+    elements is written as <name>.npy = its elements at DUMP_CAP sorted positions drawn once
+    from a fixed seed (the same positions for the same length) and <name>_blocksum.npy = the
+    sum of every DUMP_BLOCK consecutive elements, so every element still counts."""
+    os.makedirs(d, exist_ok=True)
+    sfx = f".rank{rank}" if world > 1 else ""
+    files = {}
+    for name, t in arrays.items():
+        t = t.reshape(-1)
+        dt = np.float32 if t.element_size() <= 2 else np.float64
+        if t.numel() > DUMP_CAP:
+            sums = []
+            for o in range(0, t.numel(), 1 << 26):   # (bounded temporaries)
+                v = t[o: o + (1 << 26)]
+                k = v.numel() // DUMP_BLOCK * DUMP_BLOCK
+                sums.append(v[:k].view(-1, DUMP_BLOCK).sum(dim=1, dtype=torch.int64))
+                if k < v.numel():
+                    sums.append(v[k:].sum(dtype=torch.int64).reshape(1))
+            files[name + "_blocksum"] = torch.cat(sums).cpu().numpy().astype(np.float64)
+            idx = np.sort(np.random.default_rng(0xD0).integers(0, t.numel(), DUMP_CAP))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        files[name] = t.cpu().numpy().astype(dt)
+    total = sum(v.nbytes for v in files.values())
+    if total > DUMP_LIMIT:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT} byte limit")
+    for name, v in files.items():
+        np.save(os.path.join(d, f"{name}{sfx}.npy"), v)
+
+
+def huffman_outputs(lane, world):
+    """What the lane's last step returned: the payload bytes and bit count, the sync index
+    (group bases, chunk bit lengths) and the decoded bytes."""
+    with torch.cuda.stream(lane.stream):
+        s = lane.state["s"]
+        base = s.bit_base if isinstance(s.bit_base, int) else int(s.bit_base.item())
+        bits = s.bits if s.bits >= 0 else int(lane.total.item())
+        payload = s.words[: (base % 32 + bits + 31) // 32].view(torch.uint8)
+        if world == 1:   # (a shard's first and last word may hold a neighbour's bits: kept whole)
+            payload = payload[: (bits + 7) // 8]
+        return {"payload": payload, "payload_bits": torch.tensor([bits], dtype=torch.int64),
+                "sync_bases": s.sync[0], "sync_lens": s.sync[1], "decoded": lane.state["dec"]}
 
 
 NYB_METRIC = "GB/s nybble encode+decode on 1 GiB byte stream per MI355X; % HBM roofline"
@@ -303,6 +391,23 @@ def main_nybble(a, dev, rank, world):
     run_steps(lanes, a.prewarm + a.warmup, True)
     torch.cuda.synchronize()
     ms_step = timed_steps(lanes, a.steps, True, world, dev)
+    if a.dump_outputs:   # the last timed step's compressed stream (static: and what it decoded to)
+        last = lanes[(a.steps - 1) % len(lanes)].st
+        dump_outputs(a.dump_outputs, {"compressed": last["comp"], **({} if modify else {"decoded": last["y"]})},
+                     rank, world)
+    res = headline(a, world, n, ms_step, lanes)
+    res["metric"] = NYB_METRIC if not modify else NYB_METRIC.replace("encode+decode", "encode")
+    res["config"] = {"workload": f"nybble {'adaptive (nybble_compress)' if modify else 'static (compress_bytestring)'}"
+                                 f" on {n >> 20} MiB of C1 English-like text per GPU"
+                                 + ("; encode per step (decode: sequential, decode_sample)" if modify else
+                                    "; encode + decode per step"),
+                     "codec": "nybble", "mode": a.mode, "bytes_per_gpu": n,
+                     "parallelism": f"replica{world}" if world > 1 else "single"}
+    if not a.full:
+        return finish(res, rank, world)
+    if a.dump_outputs:   # the dump broke the run of steps: warm up again before the measurements below
+        run_steps(lanes, a.warmup, True)
+        torch.cuda.synchronize()
     ms_serial = timed_steps(lanes[:1], a.steps, False, world, dev) if len(lanes) > 1 else ms_step
     torch.cuda.set_stream(lane0.stream)   # the rest runs on lane 0 (its codec's stream)
     m = st["comp"].numel()
@@ -393,21 +498,8 @@ def main_nybble(a, dev, rank, world):
         traffic, traffic_src = pmc_traffic(kname.split("<")[0], argparse.Namespace(cfg=wl, nary=0), n)
     kern_sum = sum(float(np.sum(v)) for v in per.values()) / a.profile_steps
     enc_frac = (n + m) / (enc_ms * 1e-3) / HBM_PEAK
-    res = {
-        "metric": NYB_METRIC if not modify else NYB_METRIC.replace("encode+decode", "encode"),
-        "value": round(world * n / (ms_step * 1e-3) / 1e9, 2),
-        "unit": "GB/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "prewarm": a.prewarm,
-        "ms_per_step": round(ms_step, 4),
-        "in_flight": len(lanes),
-        "in_flight_inputs": "distinct",
-        "ms_per_step_serial": round(ms_serial, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "u8", "data": "synthetic",
-        "config": {"workload": f"nybble {'adaptive (nybble_compress)' if modify else 'static (compress_bytestring)'}"
-                               f" on {n >> 20} MiB of C1 English-like text per GPU"
-                               + ("; encode per step (decode: sequential, decode_sample)" if modify else
-                                  "; encode + decode per step"),
-                   "codec": "nybble", "mode": a.mode, "bytes_per_gpu": n,
-                   "parallelism": f"replica{world}" if world > 1 else "single"},
+    res.update({
+        "ms_per_step_serial": round(ms_serial, 4),
         "roofline": {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 1), "peak": HBM_PEAK / 1e9,
                      "unit": "GB/s", "frac": round(achieved * 1e9 / HBM_PEAK, 4), "traffic": traffic,
                      "traffic_source": traffic_src, "alg_bytes_per_launch": dom_bytes, "mean_ms": round(dom_ms, 4),
@@ -417,7 +509,7 @@ def main_nybble(a, dev, rank, world):
         "ratio": round(m / n, 4),
         "kernels": kernels,
         "roundtrip_ok": ok,
-    }
+    })
     if dec_ms is not None:
         res["roofline"].update({"decode_frac": round((m + n) / (dec_ms * 1e-3) / HBM_PEAK, 4),
                                 "decode_ms": round(dec_ms, 4)})
@@ -429,10 +521,7 @@ def main_nybble(a, dev, rank, world):
         res["decode_batch"] = dec_batch
     if rank == 0 and world == 1 and not a.no_cpu:
         res["cpu_baseline"] = cpu_baseline_nybble(x, a, modify)
-    if rank == 0:
-        print(json.dumps(res), flush=True)
-    if world > 1:
-        dist.destroy_process_group()
+    finish(res, rank, world)
 
 
 class NybLane:

@@ -1,4 +1,4 @@
-"""One-line summary of a bench.py JSON line on stdin."""
+"""One-line summary of a `bench.py --full` JSON line on stdin."""
 import json
 import sys
 

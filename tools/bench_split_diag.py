@@ -36,5 +36,5 @@ def split(enc, dec, k):
 
 
 bench.split_timed, bench.timed_steps = split, timed
-sys.argv = ["bench.py"] + sys.argv[1:]
+sys.argv = ["bench.py", "--full"] + sys.argv[1:]   # (the split is part of the --full run)
 bench.main()

@@ -12,7 +12,7 @@ mkdir -p gpurun_out
 run() {   # N PORT LOG extra-args...
   local N=$1 P=$2 LOG=$3; shift 3
   DC_BENCH_BACKEND=gloo DC_BENCH_PHASES=1 DC_BENCH_TRACE_AFTER=30 timeout -k 10 280 python -m torch.distributed.run --nnodes=1 \
-    --nproc-per-node $N --master-addr 127.0.0.1 --master-port $P bench.py --gpus $N --steps 5 --warmup 2 --prewarm 5 --no-cpu "$@" > $LOG 2>&1
+    --nproc-per-node $N --master-addr 127.0.0.1 --master-port $P bench.py --gpus $N --full --steps 5 --warmup 2 --prewarm 5 --no-cpu "$@" > $LOG 2>&1
   local rc=$?
   grep -E '^\{' $LOG | python -c "import json,sys; d=json.loads(sys.stdin.read()); k=d['kernels']; print('N', d['n_gpus'], 'value', d['value'], 'ms', d['ms_per_step'], 'table', d.get('table_mode'), 'launches/step', sum(v['launches_per_step'] for v in k.values()), {n: v['launches_per_step'] for n, v in k.items()}, 'gather', d.get('gather'), 'ok', d['roundtrip_ok'])" || true
   grep -E "rank [0-9]\]" $LOG | tail -8

@@ -4,8 +4,8 @@ set -o pipefail
 cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp
 TAG=${1:-verify}
-CPU=--no-cpu
-[ "$2" = "--cpu" ] && CPU=
+CPU="--full --no-cpu"
+[ "$2" = "--cpu" ] && CPU=--full
 mkdir -p gpurun_out
 timeout -k 10 600 python -u -m pytest tests/ -m gpu -q --timeout 200 --timeout-method thread > gpurun_out/${TAG}_gpu_tests.log 2>&1
 rc=$?

@@ -4,7 +4,7 @@
 set -o pipefail
 export TMPDIR=/tmp
 OUT=${1:-gpurun_out/pmc}; shift
-ARGS=${@:---no-cpu --steps 2 --warmup 1 --profile-steps 1}
+ARGS=${@:---full --no-cpu --steps 2 --warmup 1 --profile-steps 1}
 mkdir -p $OUT
 rocprofv3 -L > $OUT/counters_list.txt 2>&1 || true
 i=0
