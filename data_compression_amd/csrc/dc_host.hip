@@ -410,7 +410,9 @@ uint64_t dc_huff_netstring_bound(uint64_t n)
 int dc_huff_compress_netstring(const uint8_t *in, uint64_t n, int n_ary, const int32_t *lengths, int max_symbol_value,
                                uint32_t sync_syms, uint8_t *out, uint64_t cap, uint64_t *out_len)
 {
-    if ((n && !in) || !out || !out_len || n_ary < 2 || n_ary > 16) return DC_E_ARG;
+    // every arity the table kernel takes (dc_huff_table: 2..256): the blocks carry n as text and
+    // the payload as bits, so nothing here depends on the digit width
+    if ((n && !in) || !out || !out_len || n_ary < 2 || n_ary > 256) return DC_E_ARG;
     if (lengths && (max_symbol_value < 0 || max_symbol_value >= DC_MAX_SYMS)) return DC_E_ARG;
     if (sync_syms != 0 && (sync_syms < 16 || sync_syms > DC_SYNC_MAX || (sync_syms & (sync_syms - 1))))
         return DC_E_ARG;
@@ -547,7 +549,7 @@ int dc_huff_decompress_netstring(const uint8_t *in, uint64_t m, uint8_t *out, ui
     };
     auto flush = [&]() -> int {   // decode the finished Huffman segment into d_dst + dpos
         if (!seg.have_meta && !seg.zchars) return DC_OK;
-        if (!seg.have_meta || !seg.have_table || seg.nary < 2 || seg.nary > 16) return DC_E_STREAM;
+        if (!seg.have_meta || !seg.have_table || seg.nary < 2 || seg.nary > 256) return DC_E_STREAM;
         const uint32_t S = (uint32_t)seg.S;
         if (S < 16 || S > DC_SYNC_MAX || (S & (S - 1)) || seg.zchars != (seg.bits + 5) / 6) return DC_E_STREAM;
         const uint64_t ng = dc_huff_sync_groups(seg.syms, S), nc = dc_huff_sync_chunks(seg.syms, S);

@@ -18,6 +18,8 @@ Reference functions exercised (file:line in /root/reference):
   digit2int                          n_ary_huffman.c:430-455
   compress / decompress (static; via oracle/ref_shim.c wrappers)
                                      n_ary_huffman.c:1688-1815, :2014-2094
+  huffman / convert_lengths_to_encode_table / the tree helpers at arities 2..256 and
+  max_leaf_value up to 1023 (huffman_wide.npz; `gen_golden.py wide` regenerates it alone)
 """
 from __future__ import annotations
 
@@ -393,8 +395,189 @@ def gen_helpers(rng):
     print("helpers: %d nybble cases, %d trees" % (len(cb), len(trees)))
 
 
+WIDE_NARY = tuple(range(2, 34)) + (64, 100, 255, 256)
+WIDE_SPREAD = (2, 3, 7, 16, 17, 31, 32, 33, 64, 100, 255, 256)   # both sides of 32 (wave merge / serial merge)
+WIDE_MID = (2, 7, 17, 32, 33, 64, 256)
+WIDE_SMALL_M = (2, 3, 20, 300, 511, 512, 513, 767)
+WIDE_MODES = ("ties", "wide", "all", "sparse")
+WIDE_TREE_NARY = (2, 6, 17, 32, 33, 100, 256)
+
+
+def wide_nodes(M, k, n):
+    """(dummies, nodes the reference's list holds when generate_huffman_tree is done): M + 1
+    leaves, the dummy leaves (n_ary_huffman.c:900-903) and one internal node per merge."""
+    dummies = (n - 1) - ((k - 1) % (n - 1))
+    return dummies, M + 1 + dummies + (k + dummies - 1) // (n - 1)
+
+
+def wide_fits(M, k, n):
+    """The reference writes list[2 * M] unchecked (huffman(), :1168; NDEBUG): a case is run
+    only when its whole tree fits. The drop-in reports DC_E_CAPACITY past the same bound."""
+    return k >= 1 and wide_nodes(M, k, n)[1] <= 2 * M
+
+
+def wide_freq(rng, M, n, mode):
+    """Counts for indices 0..M. Symbol 0 stays 0 (the reference's C strings never hold it);
+    symbol M is counted only in the "top" mode (the index-M quirk, :1336 / :1421)."""
+    f = np.zeros(M + 1, dtype=np.int64)
+    if mode == "all":
+        # every symbol 1..M; at n = 2 (one node per symbol) the two highest stay 0, or the
+        # tree needs 2 * M + 2 nodes
+        hi = M - 2 if n == 2 else M
+        f[1: hi + 1] = rng.integers(1, 4, size=hi)
+        return f
+    pool = np.arange(1, M)
+    if mode == "sparse":
+        k = min(int(rng.integers(1, 7)), pool.size)
+        idx = rng.choice(pool, size=k, replace=False)
+        f[idx] = rng.integers(1, 100, size=k)
+        return f
+    if mode == "sums":
+        # counts 1, n and n * n: the first nodes made of n ones count n, so internal nodes tie with
+        # leaves (and later nodes with n * n), and the order on equal counts (a leaf before an
+        # internal node, :672-731) decides the tree. Counts 1..3 never tie with a node at n > 3
+        k = int(rng.integers(pool.size // 2, pool.size + 1)) - (2 if n == 2 else 0)
+        idx = rng.choice(pool, size=k, replace=False)
+        f[idx] = rng.choice([1, n, n * n], size=k, p=[0.6, 0.3, 0.1])
+        return f
+    # n = 2 makes one node per symbol: more than M - 2 symbols need more than 2 * M nodes
+    kmax = pool.size if n != 2 else M - 2 - (mode == "top")
+    k = int(rng.integers(2, kmax + 1)) if kmax >= 2 else max(kmax, 0)
+    idx = rng.choice(pool, size=k, replace=False)
+    f[idx] = rng.integers(1, 4, size=k) if mode in ("ties", "top") else rng.integers(1, 1_000_001, size=k)
+    if mode == "top":
+        f[M] = int(rng.integers(1, 4))
+    return f
+
+
+def gen_huffman_wide(rng):
+    """huffman (n_ary_huffman.c:1161) and convert_lengths_to_encode_table (:1382) at every
+    arity 2..33 and 64, 100, 255, 256, and alphabets max_leaf_value 2..1023, with the case's own
+    max_leaf_value and arrays of M + 1 ints; and the node lists of setup_nodes (:773) /
+    generate_huffman_tree (:868) / summarize_tree_with_lengths (:1033) with list_length 2 * M.
+    Ragged arrays are stored concatenated, case i at [off[i], off[i + 1])."""
+    lib = load("libref_huffman.so")
+    plan = []
+    for i, n in enumerate(WIDE_NARY):
+        plan.append((1023, n, "all"))
+        plan.append((258, n, WIDE_MODES[i % 4]))   # each mode on both sides of n = 32
+    for M in WIDE_SMALL_M:
+        if M <= 20:
+            plan += [(M, n, mode) for n in WIDE_SPREAD for mode in WIDE_MODES]
+            continue
+        # (the file's size: two modes per arity, and wide counts at M >= 511 only at n = 17 and 256)
+        for j, n in enumerate(WIDE_MID):
+            other = ("ties", "sparse", "wide")[j % 3]
+            if other == "wide" and M >= 511 and n not in (17, 256):
+                other = "ties"
+            plan += [(M, n, "all"), (M, n, other)]
+    for n in (2, 17, 32, 33, 256):
+        plan += [(1023, n, "ties")] * (n in (2, 33, 256)) + [(1023, n, "sparse")]
+    plan += [(1023, 2, "wide")]
+    for M, ns_top in ((20, (2, 3, 16, 17)), (300, (2, 3, 16, 17, 33, 256)), (258, (2, 33)), (1023, (3, 33))):
+        plan += [(M, n, "top") for n in ns_top]
+    plan += [(258, n, "sums") for n in (2, 6, 17, 24, 32, 33, 64, 100, 256)] + [(1023, 33, "sums"), (1023, 256, "sums")]
+    # sparse cases of exactly one and two symbols
+    for n in (2, 17, 33, 256):
+        for k in (1, 2):
+            plan.append((258, n, "k%d" % k))
+
+    Ms, ns, modes, freqs, lens, encl, encv, items, dropped = [], [], [], [], [], [], [], [], []
+    for M, n, mode in plan:
+        if mode in ("k1", "k2"):
+            f = np.zeros(M + 1, dtype=np.int64)
+            f[[65, 200][: int(mode[1])]] = 7
+            mode = "sparse"
+        else:
+            f = wide_freq(rng, M, n, mode)
+        k = int(np.count_nonzero(f))
+        if not wide_fits(M, k, n):
+            dropped.append((M, n, mode))
+            continue
+        fr = (C.c_int * (M + 1))(*[int(v) for v in f])
+        out = (C.c_int * (M + 1))()
+        lib.huffman(M, fr, n, out)
+        L = np.array(out[:], dtype=np.int32)
+        el, ev = ref_canonical(lib, L, n, max_sym=M)
+        Ms.append(M); ns.append(n); modes.append(mode); items.append(k + wide_nodes(M, k, n)[0])
+        freqs.append(f); lens.append(L); encl.append(el); encv.append(ev)
+    print("wide cases: %d recorded, %d dropped by the bounds rule" % (len(Ms), len(dropped)))
+    print("  dropped (M, n): " + " ".join(sorted({"%d/%d" % (M, n) for M, n, _ in dropped},
+                                                 key=lambda s: [int(v) for v in s.split("/")])))
+    assert not [d for d in dropped if d[0] >= 258 and d[1] <= 33], "the bounds rule dropped a case it must not"
+
+    # the coverage this fixture is for
+    have = set(zip(Ms, ns, modes))
+    cases = list(zip(Ms, ns, modes, freqs, items))
+    for n in WIDE_NARY:
+        big = [c for c in cases if c[0] == 1023 and c[1] == n and c[2] == "all"]
+        # k = 1023 > 512: the bitonic sort (n = 2: 1021, the most its tree's 2 * M nodes allow)
+        assert big and np.count_nonzero(big[0][3]) == (1021 if n == 2 else 1023) and big[0][3].max() <= 3, n
+        assert any(c[0] == 258 and c[1] == n for c in cases), n
+    for M in WIDE_SMALL_M:
+        got = sorted({c[1] for c in cases if c[0] == M})
+        if M == 2:
+            assert not got   # 3 leaves + a dummy + a root > 4 nodes: no arity fits, all dropped
+        elif M == 3:
+            assert got and max(got) <= 4   # 6 nodes: one merge, so n <= 4
+        else:
+            assert any(n <= 32 for n in got) and any(n > 32 for n in got), (M, got)
+    for side in (lambda n: n <= 32, lambda n: n > 32):
+        assert {c[2] for c in cases if side(c[1])} >= set(WIDE_MODES) | {"top", "sums"}
+    ks = {int(np.count_nonzero(c[3])) for c in cases if c[2] == "sparse"}
+    assert {1, 2} <= ks and max(ks) <= 6, ks
+    it511 = [c[4] for c in cases if c[0] == 511 and c[2] == "all"]
+    it513 = [c[4] for c in cases if c[0] == 513 and c[2] == "all"]
+    # the rank sort / bitonic sort threshold: items 510, 512 and 513 among them
+    assert min(it511) <= 512 < max(it513) and {512, 513} <= set(it511 + it513), (it511, it513)
+    assert any(c[3][c[0]] > 0 and c[0] != 258 for c in cases)   # symbol M itself counted
+
+    # whole node lists (as gen_helpers, list_length = 2 * M)
+    lib.setup_nodes.argtypes = [C.c_int, C.POINTER(Node), C.c_int, C.POINTER(C.c_int)]
+    lib.generate_huffman_tree.argtypes = [C.c_int, C.POINTER(Node), C.c_int, C.c_int]
+    lib.summarize_tree_with_lengths.argtypes = [C.c_int, C.POINTER(Node), C.c_int, C.POINTER(C.c_int), C.c_int]
+    tplan = [(M, n, "all" if M == 1023 else "ties") for n in WIDE_TREE_NARY for M in (258, 1023)]
+    tplan += [(20, 3, "all"), (20, 6, "all")]   # tie-heavy small ones
+    tplan += [(258, n, "sums") for n in (17, 33, 256)]   # leaves tied with internal nodes
+    tM, tn, tfreq, tsetup, tnodes, tlens = [], [], [], [], [], []
+    for M, n, mode in tplan:
+        f = wide_freq(rng, M, n, mode)
+        assert wide_fits(M, int(np.count_nonzero(f)), n), (M, n)
+        LL = 2 * M
+        fr = (C.c_int * (M + 1))(*[int(v) for v in f])
+        lst = (Node * LL)()
+        lib.setup_nodes(LL, lst, M, fr)
+        tsetup.append(nodes_array(lst))
+        lib.generate_huffman_tree(LL, lst, n, M)
+        tnodes.append(nodes_array(lst))
+        L = (C.c_int * (M + 1))()
+        lib.summarize_tree_with_lengths(LL, lst, M, L, M + 1)
+        tM.append(M); tn.append(n); tfreq.append(f); tlens.append(np.array(L[:], dtype=np.int32))
+    assert max(int(L.max()) for L in lens + tlens) < 2 ** 15
+
+    def cat(arrs, dtype):
+        return np.concatenate(arrs).astype(dtype)
+
+    def offs(arrs):
+        return np.concatenate([[0], np.cumsum([len(a) for a in arrs])]).astype(np.int32)
+
+    np.savez_compressed(os.path.join(HERE, "huffman_wide.npz"),
+                        M=np.array(Ms, dtype=np.int32), n=np.array(ns, dtype=np.int32), mode=np.array(modes),
+                        off=offs(freqs), freq=cat(freqs, np.int32), lengths=cat(lens, np.int16),
+                        enc_len=cat(encl, np.int16), enc_val=cat(encv, np.uint32),
+                        tree_M=np.array(tM, dtype=np.int32), tree_n=np.array(tn, dtype=np.int32),
+                        tree_off=offs(tfreq), tree_freq=cat(tfreq, np.int32), tree_lengths=cat(tlens, np.int16),
+                        tree_row=offs(tsetup), tree_setup=cat(tsetup, np.int32), tree_nodes=cat(tnodes, np.int32))
+    print("wide: %d tables (longest length %d digits), %d trees, %d bytes"
+          % (len(Ms), max(int(L.max()) for L in lens), len(tM),
+             os.path.getsize(os.path.join(HERE, "huffman_wide.npz"))))
+
+
 def main():
     rng = np.random.default_rng(20250808)
+    if sys.argv[1:] == ["wide"]:
+        gen_huffman_wide(np.random.default_rng(20261019))
+        return
     if sys.argv[1:] == ["helpers"]:
         gen_helpers(np.random.default_rng(20251017))
         return
@@ -410,6 +593,7 @@ def main():
     gen_digits()
     gen_container(np.random.default_rng(20251016))
     gen_helpers(np.random.default_rng(20251017))
+    gen_huffman_wide(np.random.default_rng(20261019))
 
 
 if __name__ == "__main__":

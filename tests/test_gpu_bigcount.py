@@ -17,14 +17,16 @@ pytestmark = pytest.mark.gpu
 MAX_SYMS, MAX_DIGITS = 1024, 128
 
 
-class DTable(C.Structure):   # include/dc_gpu.h dc_dtable, up to the fields read here
+class DTable(C.Structure):   # include/dc_gpu.h dc_dtable, up to the fields the GPU tests read (shared)
     _fields_ = [("code", C.c_uint32 * 256), ("nbits", C.c_uint32 * 256), ("lut", C.c_uint32 * (1 << 12)),
                 ("first", C.c_uint32 * (MAX_DIGITS + 1)), ("count", C.c_uint32 * (MAX_DIGITS + 1)),
                 ("start", C.c_uint32 * (MAX_DIGITS + 1)), ("lim", C.c_uint64 * 33),
                 ("syms", C.c_uint16 * MAX_SYMS), ("lengths", C.c_int32 * MAX_SYMS),
                 ("enc_len", C.c_int32 * MAX_SYMS), ("enc_val", C.c_uint32 * MAX_SYMS),
                 ("n_ary", C.c_int32), ("w", C.c_int32), ("max_symbol_value", C.c_int32), ("max_bits", C.c_int32),
-                ("min_len", C.c_int32), ("max_len", C.c_int32), ("status", C.c_int32)]
+                ("min_len", C.c_int32), ("max_len", C.c_int32), ("status", C.c_int32), ("last_written", C.c_int32),
+                ("dlut", C.c_uint16 * (1 << 12)), ("dlut2", C.c_uint16 * 7168),
+                ("dlut2_k", C.c_int32), ("dec_ready", C.c_int32), ("fixed8", C.c_int32)]
 
 
 @pytest.fixture(scope="module")

@@ -278,6 +278,16 @@ def test_fixed8_byte_map_paths(torch_cuda, codec, bit_base, alpha):
             wb[n // 2] = 255
             codec.decode_into(enc, out)
             assert codec.decode_status() != 0
+        if alpha == "run" and bit_base == 0 and n == 100_003:
+            # the affine map with lo = 10: code 250 is past the 241 coded bytes (and 250 + lo
+            # carries out of its byte), in a full 16-byte granule and in the ragged tail
+            wb = enc["words"].view(torch.uint8)
+            for at in (n // 2, n - 1):
+                keep = wb[at].clone()
+                wb[at] = 250
+                codec.decode_into(enc, out)
+                assert codec.decode_status() != 0, at
+                wb[at] = keep   # (each case alone)
 
 
 @pytest.mark.parametrize("case", ["unaligned-out", "long-halves"])
@@ -427,7 +437,8 @@ def test_c_driver_runs(torch_cuda, name, tmp_path):
 # ---------------------------------------------------------------- decoder paths (S = 64)
 def _chain_stream(nsym, seed):
     """Symbol counts 2^0 .. 2^(nsym-1): the Huffman tree is a chain, so binary code lengths
-    reach about nsym bits and codes longer than the decoder's 12 + 8 bit two-level table occur."""
+    reach about nsym bits and codes longer than the fast decoder's 15-bit first-level table occur
+    (those chunks take the exact redo)."""
     f = [1 << i for i in range(nsym)]
     syms = np.repeat(np.arange(1, nsym + 1, dtype=np.uint8), f)
     rng = np.random.default_rng(seed)

@@ -48,6 +48,37 @@ def test_canonical_reference_known_answers():
     assert list(d["enc_val"][2][2:11]) == list(range(9))
 
 
+def _wide_cases():
+    """(M, n, mode, freq, lengths, enc_len, enc_val) of tests/golden/huffman_wide.npz: arities
+    2..33, 64, 100, 255, 256 and alphabets max_leaf_value 3..1023 (gen_golden.py gen_huffman_wide)."""
+    d = _load("huffman_wide.npz")
+    off = d["off"]
+    for i in range(len(d["n"])):
+        a, b = int(off[i]), int(off[i + 1])
+        assert b - a == int(d["M"][i]) + 1
+        yield (int(d["M"][i]), int(d["n"][i]), str(d["mode"][i]), d["freq"][a:b], d["lengths"][a:b],
+               d["enc_len"][a:b], d["enc_val"][a:b])
+
+
+def test_wide_huffman_lengths_match_reference():
+    bad, seen = [], 0
+    for M, n, mode, f, L, _, _ in _wide_cases():
+        got = orc.huffman_lengths(f.astype(np.uint64), n, max_leaf=M)
+        seen += 1
+        if not np.array_equal(got, L):
+            bad.append((M, n, mode))
+    assert seen > 200 and not bad, bad[:10]
+
+
+def test_wide_canonical_codes_match_reference():
+    bad = []
+    for M, n, mode, _, L, el_ref, ev_ref in _wide_cases():
+        el, ev = orc.canonical(L.astype(np.int32), n, max_sym=M)
+        if not (np.array_equal(el, el_ref) and np.array_equal(ev, ev_ref)):
+            bad.append((M, n, mode))
+    assert not bad, bad[:10]
+
+
 def test_histogram_matches_reference():
     d = _load("histogram.npz")
     for x, h in zip(d["inputs"], d["counts"]):
