@@ -112,6 +112,8 @@ def _declare_core(L):
         "dc_huff_block_hist": ([vp, P, u64], i32),
         "dc_huff_decode": ([vp, P, u64, u64, P, P, u32, u64, P, P], i32),
         "dc_huff_decode_dev": ([vp, P, P, u64, P, P, u32, u64, P, P], i32),
+        "dc_huff_decode_ranges": ([vp, P, u64, u64, P, P, u32, u64, P, P, P, P, u64, P, u64], i32),
+        "dc_huff_decode_range": ([vp, P, u64, u64, P, P, u32, u64, P, u64, u64, P], i32),
         "dc_huff_decode_status": ([vp], i32),
         "dc_huff_decode_redo_count": ([vp, C.POINTER(u64)], i32),
         "dc_huff_base64url": ([vp, P, u64, u64, P], i32),
@@ -148,6 +150,8 @@ def _declare_core(L):
         "dc_huff_decompress_netstring": ([u8p, u64, u8p, u64, C.POINTER(u64)], i32),
         "dc_huff_netstring_info": ([u8p, u64, C.POINTER(u64)], i32),
         "dc_huff_container_info": ([u8p, u64, C.POINTER(u64), C.POINTER(i32), C.POINTER(u64)], i32),
+        "dc_huff_range_span": ([u64, u32, C.POINTER(u64), u64, u64, u64, C.POINTER(u64)], i32),
+        "dc_huff_decompress_range_host": ([u8p, u64, u64, u64, u8p, u64, C.POINTER(u64)], i32),
         "dc_nyb_compress_host": ([u8p, u64, i32, u8p, u64, C.POINTER(u64)], i32),
         "dc_nyb_decompress_host": ([u8p, u64, i32, u8p, u64, C.POINTER(u64)], i32),
         "dc_small_compress_host": ([u8p, u64, u8p, u64, C.POINTER(u64)], i32),

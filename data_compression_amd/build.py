@@ -50,7 +50,7 @@ def _stale(target, deps):
 def build(force: bool = False, verbose: bool = False) -> None:
     os.makedirs(LIB, exist_ok=True)
     headers = [os.path.join(INC, h) for h in os.listdir(INC) if h.endswith(".h")]
-    hdr_local = [os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".h")]
+    hdr_local = [os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith((".h", ".inc"))]   # included sources too
     core = os.path.join(LIB, "libdc_core.so")
     core_deps = [os.path.join(CSRC, s) for s in CORE_SRC] + headers + hdr_local
     objs = []

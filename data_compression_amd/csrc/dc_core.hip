@@ -6259,6 +6259,8 @@ __global__ __launch_bounds__(256) void k_copy_probe(const uint4 *__restrict__ sr
     for (; i < n16; i += stride) st_nt(dst + i, ld_nt(src + i));
 }
 
+#include "dc_range_kernels.inc"
+
 #ifdef DC_AB_KERNELS
 #include "dc_ab_kernels.inc"
 #endif
@@ -6289,6 +6291,7 @@ struct dc_ctx {
     uint32_t *d_fix;        size_t fix_cap;       // decode redo: a u64 chunk mask per group
     uint32_t *d_fixpos;     size_t fixpos_cap;    // decode redo: bit offset of a flagged chunk
     uint64_t last_groups;                         // groups of the last S = 64 decode (redo mask length)
+    uint64_t *d_rng;        size_t rng_cap;       // range decode: items per range, then their offsets (+ total)
     uint64_t *d_hloc;                             // this context's last histogram (256 u64; hist[] may be all-reduced)
     const dc_dtable *plan_table;                  // the table and device total of the last plan
     uint64_t *plan_total;
@@ -6473,6 +6476,7 @@ void dc_ctx_destroy(dc_ctx *c)
     if (c->d_queue) (void)hipFree(c->d_queue);
     if (c->d_fix) (void)hipFree(c->d_fix);
     if (c->d_fixpos) (void)hipFree(c->d_fixpos);
+    if (c->d_rng) (void)hipFree(c->d_rng);
     if (c->d_scr) (void)hipFree(c->d_scr);
     if (c->d_meta) (void)hipFree(c->d_meta);
     if (c->d_summ) (void)hipFree(c->d_summ);
@@ -7169,7 +7173,70 @@ int dc_huff_decode_status(dc_ctx *c)
     int v = 0;
     HIPCHK(hipMemcpyAsync(&v, dec_err(c), sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
+    if (v == RNG_BAD_RANGE) return DC_E_ARG;   // (dc_huff_decode_ranges) only a bad range: the others are decoded
     return v ? DC_E_STREAM : DC_OK;
+}
+
+// (5r) random access by the sync index (dc_range_kernels.inc)
+static int range_args(dc_ctx *c, const uint32_t *d_words, uint64_t words, const uint64_t *d_sync_base,
+                      const uint16_t *d_sync_len, uint32_t S, const dc_dtable *d_table)
+{
+    if (!c || !d_table || !d_words || !d_sync_base || !d_sync_len) return DC_E_ARG;
+    if (!sync_ok(S)) return DC_E_ARG;
+    if (((uintptr_t)d_words) & 15) return DC_E_ARG;
+    if (words < 4) return DC_E_ARG;
+    return DC_OK;
+}
+
+int dc_huff_decode_ranges(dc_ctx *c, const uint32_t *d_words, uint64_t bit_base, uint64_t words,
+                          const uint64_t *d_sync_base, const uint16_t *d_sync_len, uint32_t S, uint64_t n,
+                          const dc_dtable *d_table, const uint64_t *d_first, const uint64_t *d_count,
+                          const uint64_t *d_out_off, uint64_t nranges, uint8_t *d_out, uint64_t out_cap)
+{
+    if (!c || !d_table) return DC_E_ARG;
+    if (nranges == 0) return DC_OK;
+    if (!d_first || !d_count || !d_out_off || (!d_out && out_cap) || nranges > DC_RANGES_MAX) return DC_E_ARG;
+    if (const int r = range_args(c, d_words, words, d_sync_base, d_sync_len, S, d_table)) return r;
+    if (ensure((void **)&c->d_rng, &c->rng_cap, (2 * nranges + 2) * sizeof(uint64_t))) return DC_E_HIP;
+    uint64_t *const items = c->d_rng, *const off = c->d_rng + nranges;
+    ++c->gen_d;   // the error slot, as decode_impl
+    int *const derr = dec_err(c), *const derr_next = dec_err_next(c);
+    if (!dec_tables_fresh(c, d_table)) LAUNCH(c, "dec_tables", k_dec_tables, 1, 256, const_cast<dc_dtable *>(d_table), derr);
+    LAUNCH(c, "huff_range_items", k_range_items, (nranges + 255) / 256, 256, d_first, d_count, d_out_off, nranges, n,
+           out_cap, S, items, derr);
+    LAUNCH(c, "huff_range_scan", k_scan_u64, 1, 1024, (const uint64_t *)items, nranges, off);
+    // persistent: the item total stays on the device; no more workgroups than the ranges can fill
+    const uint64_t groups = dc_huff_sync_groups(n, S);
+    uint64_t grid = 256;
+    if (groups < 256 * DEC_WAVES && nranges < 256 * DEC_WAVES) {
+        const uint64_t most = (nranges * groups + DEC_WAVES - 1) / DEC_WAVES;
+        grid = most < 256 ? (most ? most : 1) : 256;
+    }
+    LAUNCH(c, "huff_decode_ranges", k_huff_decode_ranges, grid, DEC_WAVES * 64, d_words, bit_base, words, d_sync_base,
+           d_sync_len, S, n, d_table, d_first, d_count, d_out_off, (const uint64_t *)off, nranges, (uint64_t)0, (uint64_t)0,
+           d_out, derr, derr_next);
+    return DC_OK;
+}
+
+int dc_huff_decode_range(dc_ctx *c, const uint32_t *d_words, uint64_t bit_base, uint64_t words,
+                         const uint64_t *d_sync_base, const uint16_t *d_sync_len, uint32_t S, uint64_t n,
+                         const dc_dtable *d_table, uint64_t first, uint64_t count, uint8_t *d_out)
+{
+    if (!c || !d_table) return DC_E_ARG;
+    if (first > n || count > n - first) return DC_E_ARG;
+    if (count && !d_out) return DC_E_ARG;
+    if (const int r = range_args(c, d_words, words, d_sync_base, d_sync_len, S, d_table)) return r;
+    ++c->gen_d;
+    int *const derr = dec_err(c), *const derr_next = dec_err_next(c);
+    if (!dec_tables_fresh(c, d_table)) LAUNCH(c, "dec_tables", k_dec_tables, 1, 256, const_cast<dc_dtable *>(d_table), derr);
+    const uint32_t glog = (uint32_t)__builtin_ctz(S) + DC_SYNC_GROUP_LOG;
+    const uint64_t items = count ? ((first + count - 1) >> glog) - (first >> glog) + 1 : 0;
+    const uint64_t wgs = (items + DEC_WAVES - 1) / DEC_WAVES;
+    const uint64_t grid = wgs < 256 ? (wgs ? wgs : 1) : 256;   // (count 0: one workgroup turns the error slot over)
+    LAUNCH(c, "huff_decode_ranges", k_huff_decode_ranges, grid, DEC_WAVES * 64, d_words, bit_base, words, d_sync_base,
+           d_sync_len, S, n, d_table, (const uint64_t *)nullptr, (const uint64_t *)nullptr, (const uint64_t *)nullptr,
+           (const uint64_t *)nullptr, (uint64_t)1, first, count, d_out, derr, derr_next);
+    return DC_OK;
 }
 
 int dc_huff_text_bits(int format, int n_ary) { return text_bits(format, n_ary); }

@@ -13,6 +13,7 @@
 
 #include "dc_gpu.h"
 #include "dc_host.h"
+#include "dc_range_span.h"
 
 namespace {
 
@@ -236,6 +237,80 @@ int dc_huff_decompress_host(const uint8_t *in, uint64_t m, uint8_t *out, uint64_
     RC(dc_huff_decode_status(c));
     RC(dc_memcpy_d2h(c, out, s->out.p, n));
     *out_len = n;
+    return DC_OK;
+}
+
+int dc_huff_range_span(uint64_t n, uint32_t sync_syms, const uint64_t *h_sync_base, uint64_t end_bit, uint64_t first,
+                       uint64_t count, uint64_t out[4])
+{
+    return dc_range_span_calc(n, sync_syms, h_sync_base, end_bit, first, count, out) ? DC_E_ARG : DC_OK;
+}
+
+// A stream suffix that starts at a group boundary is itself a stream of the device ABI
+// (bit_base = that group's base, the index pointers advanced to it, the symbols counted from
+// it): only the index entries of groups g0..g1 and their payload bytes are uploaded.
+int dc_huff_decompress_range_host(const uint8_t *in, uint64_t m, uint64_t first, uint64_t count, uint8_t *out,
+                                  uint64_t cap, uint64_t *out_len)
+{
+    if (!in || !out_len) return DC_E_ARG;
+    if (m < 4 || get32(in) != kMagic) return DC_E_ARG;   // a netstring container: its index is base64url text
+    uint64_t n = 0, bits = 0;
+    int nary = 0;
+    RC(dc_huff_container_info(in, m, &n, &nary, &bits));
+    const uint32_t S = get32(in + 24);
+    if (S < 16 || S > DC_SYNC_MAX || (S & (S - 1)) || nary < 2) return DC_E_STREAM;
+    const uint64_t ng = dc_huff_sync_groups(n, S), nc = dc_huff_sync_chunks(n, S);
+    const uint64_t ib = index_bytes(n, S);
+    const uint64_t nbytes = (bits + 7) / 8;
+    if (kHeader + ib + nbytes > m) return DC_E_STREAM;
+    if (first > n || count > n - first) return DC_E_ARG;
+    if (count > cap) return DC_E_CAPACITY;
+    *out_len = 0;
+    if (count == 0) return DC_OK;
+    if (!out) return DC_E_ARG;
+    // the group bases, read in place when the container is 8-B aligned in memory
+    std::vector<uint64_t> copy;
+    const uint64_t *bases = reinterpret_cast<const uint64_t *>(in + kHeader);
+    if (((uintptr_t)in) & 7) {
+        copy.resize(ng);
+        memcpy(copy.data(), in + kHeader, ng * 8);
+        bases = copy.data();
+    }
+    uint64_t sp[4];
+    RC(dc_huff_range_span(n, S, bases, bits, first, count, sp));
+    const uint64_t g0 = sp[0], g1 = sp[1], b0 = sp[2], b1 = sp[3];
+    if (b0 > b1 || b1 > bits) return DC_E_STREAM;
+    HostState *s;
+    RC(state(&s));
+    dc_ctx *c = s->ctx;
+    int32_t lens[259];
+    for (int i = 0; i < 256; ++i) lens[i] = in[32 + i];
+    lens[256] = lens[257] = lens[258] = 0;
+    RC(s->lens.need(sizeof(lens)));
+    RC(s->table.need(sizeof(dc_dtable)));
+    RC(dc_memcpy_h2d(c, s->lens.p, lens, sizeof(lens)));
+    dc_dtable *d_tab = (dc_dtable *)s->table.p;
+    RC(dc_huff_table_lengths(c, (const int32_t *)s->lens.p, 258, nary, d_tab));
+    const int st = dc_huff_table_status(c, d_tab, nullptr);
+    if (st) return st;
+    const uint64_t gsyms = 64ull * S;
+    const uint64_t ngr = g1 - g0 + 1, c0 = 64 * g0, c1 = 64 * (g1 + 1) < nc ? 64 * (g1 + 1) : nc;
+    const uint64_t p0 = (b0 >> 5) * 4, p1 = (b1 + 7) / 8;   // payload bytes, from the word holding bit b0
+    const uint64_t words = dc_huff_words_needed(b0, b1 - b0);
+    RC(s->in.need(words * 4 + 64));
+    RC(s->sync.need(ngr * 8 + (c1 - c0) * 2 + 16));
+    RC(s->out.need(count + 64));
+    uint64_t *d_base = (uint64_t *)s->sync.p;
+    uint16_t *d_len = (uint16_t *)(d_base + ngr);
+    RC(dc_memset(c, s->in.p, 0, words * 4));   // the decoder's slack is padding here, not the container's next bytes
+    RC(dc_memcpy_h2d(c, d_base, in + kHeader + g0 * 8, ngr * 8));
+    RC(dc_memcpy_h2d(c, d_len, in + kHeader + ng * 8 + c0 * 2, (c1 - c0) * 2));
+    if (p1 > p0) RC(dc_memcpy_h2d(c, s->in.p, in + kHeader + ib + p0, p1 - p0));
+    RC(dc_huff_decode_range(c, (const uint32_t *)s->in.p, b0, words, d_base, d_len, S, n - g0 * gsyms, d_tab,
+                            first - g0 * gsyms, count, (uint8_t *)s->out.p));
+    RC(dc_huff_decode_status(c));
+    RC(dc_memcpy_d2h(c, out, s->out.p, count));
+    *out_len = count;
     return DC_OK;
 }
 

@@ -445,6 +445,82 @@ class Codec:
     def decode_into(self, enc, out):
         self.decode(enc["words"], enc["bit_base"], enc["sync"], enc["S"], enc["n"], enc["table"], out)
 
+    # ---- random access by the sync index (dc_huff_decode_range / dc_huff_decode_ranges) ----------
+    def _range_stream(self, enc):
+        if hasattr(enc["bit_base"], "data_ptr"):
+            raise ValueError("range decode needs the stream's bit_base as an int (it is device-resident here)")
+        base, lens = enc["sync"]
+        return (_ptr(enc["words"]), int(enc["bit_base"]), enc["words"].numel(), _ptr(base), _ptr(lens), enc["S"],
+                enc["n"], _ptr(enc["table"]))
+
+    @staticmethod
+    def _u8_out(out, what):
+        if out.dtype != torch.uint8 or not out.is_contiguous():
+            raise ValueError(f"{what} output: contiguous uint8")
+        return out
+
+    def decode_range(self, enc, first: int, count: int, out=None):
+        """Symbols [first, first + count) of the stream enc (the dict of encode() /
+        small_huff_encode()) -> a uint8 device tensor of count bytes (a view of `out` when
+        given: any alignment, >= count bytes). Reads only the chunks the range touches.
+        first + count > enc["n"] raises DcError (DC_E_ARG)."""
+        stream = self._range_stream(enc)
+        first, count = int(first), int(count)
+        if first < 0 or count < 0:
+            raise ValueError("decode_range: first and count are non-negative")
+        if out is None:
+            out = self._t(max(count, 1))
+        elif self._u8_out(out, "decode_range").numel() < count:
+            raise ValueError("decode_range output holds fewer than count bytes")
+        check("dc_huff_decode_range", self.L.dc_huff_decode_range(self.ctx, *stream, first, count, _ptr(out)))
+        return out[:count]
+
+    def decode_ranges(self, enc, first, count, out=None, out_off=None):
+        """Many ranges in one call: range r = symbols [first[r], first[r] + count[r]) of the
+        stream enc -> out[out_off[r] ..). first / count / out_off: int64 device tensors (read by
+        the kernels: a gather list computed on the GPU is used as it is) or Python sequences.
+        out_off defaults to the exclusive cumulative sum of count, computed on the device (the
+        ranges packed back to back); out defaults to a new tensor that holds every range (sized
+        with one host read unless count is a Python sequence and out_off the default). Returns
+        (out, out_off). A range past the stream or past out writes nothing and makes
+        decode_status() DC_E_ARG (-1); the other ranges are decoded."""
+        stream = self._range_stream(enc)
+        dev = f"cuda:{self.device}"
+
+        def as_dev(v, name):
+            if hasattr(v, "data_ptr"):
+                if v.dtype != torch.int64 or not v.is_cuda or not v.is_contiguous():
+                    raise ValueError(f"decode_ranges {name}: a contiguous int64 device tensor")
+                return v
+            a = np.ascontiguousarray(v, dtype=np.int64).reshape(-1)
+            if a.size and a.min() < 0:
+                raise ValueError(f"decode_ranges {name}: non-negative values")
+            return torch.from_numpy(a).to(dev)
+
+        total = None   # bytes of a packed output, when the host knows the counts
+        if out_off is None and not hasattr(count, "data_ptr"):
+            total = int(np.asarray(count, dtype=np.int64).sum())
+        first, count = as_dev(first, "first"), as_dev(count, "count")
+        nr = count.numel()
+        if first.numel() != nr:
+            raise ValueError("decode_ranges: first and count differ in length")
+        if out_off is None:
+            out_off = torch.cumsum(count, 0) - count
+        else:
+            out_off = as_dev(out_off, "out_off")
+            if out_off.numel() != nr:
+                raise ValueError("decode_ranges: out_off and count differ in length")
+        if out is None:
+            if total is None:
+                total = int((out_off + count).max().item()) if nr else 0
+            buf = self._t(max(total, 1))
+            out = buf[: max(total, 0)]
+        else:
+            buf = self._u8_out(out, "decode_ranges")
+        check("dc_huff_decode_ranges", self.L.dc_huff_decode_ranges(self.ctx, *stream, _ptr(first), _ptr(count),
+                                                                    _ptr(out_off), nr, _ptr(buf), out.numel()))
+        return out, out_off
+
     # ---- C5 fused front-end encode (small_compression.c front-end, then Huffman; one pass) -----
     def small_huff_plan(self, x, n_ary: int = 16, max_symbol_value: int = 258, hist=None, table=None, total=None):
         """dc_small_huff_plan: histogram of the front-end output of x (never written), table and

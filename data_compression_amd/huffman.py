@@ -138,6 +138,34 @@ def decompress(blob: bytes, max_decompressed_size: int | None = None) -> bytes:
     return out.raw[:r]
 
 
+def range_span(n: int, sync_syms: int, sync_base, end_bit: int, first: int, count: int):
+    """dc_huff_range_span (pure host arithmetic, no device): the part of a stream that symbols
+    [first, first + count) need, as (g0, g1, first payload bit, end payload bit). sync_base:
+    the stream's u64 group bases; end_bit: bit_base + payload bits."""
+    base = np.ascontiguousarray(sync_base, dtype=np.uint64)
+    out = (C.c_uint64 * 4)()
+    rc = core().dc_huff_range_span(n, sync_syms, base.ctypes.data_as(C.POINTER(C.c_uint64)), end_bit, first, count,
+                                   out)
+    if rc:
+        raise DcError("dc_huff_range_span", rc)
+    return tuple(int(v) for v in out)
+
+
+def decompress_range(blob: bytes, first: int, count: int) -> bytes:
+    """dc_huff_decompress_range_host: bytes [first, first + count) of what a DCH1 container
+    holds, uploading only the index entries and payload bytes of the groups the range touches.
+    A netstring container (no binary index) or a range past the end raises DcError (DC_E_ARG)."""
+    if not isinstance(blob, bytes):
+        blob = bytes(blob)
+    buf = C.cast(C.c_char_p(blob), C.POINTER(C.c_uint8))   # read in place: no copy of the container
+    out = (C.c_uint8 * max(count, 1))()
+    got = C.c_uint64(0)
+    rc = core().dc_huff_decompress_range_host(buf, len(blob), first, count, out, count, C.byref(got))
+    if rc:
+        raise DcError("dc_huff_decompress_range_host", rc)
+    return bytes(out[: got.value])
+
+
 def histogram_bytes(data: bytes, max_symbol_value: int = 258) -> np.ndarray:
     """Histogram of an arbitrary byte string (NULs included), via the device API."""
     from .device import Codec

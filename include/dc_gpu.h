@@ -293,7 +293,35 @@ int dc_huff_decode(dc_ctx *ctx, const uint32_t *d_words, uint64_t bit_base, uint
 int dc_huff_decode_dev(dc_ctx *ctx, const uint32_t *d_words, const uint64_t *d_bit_base, uint64_t words,
                        const uint64_t *d_sync_base, const uint16_t *d_sync_len, uint32_t sync_syms,
                        uint64_t n, const dc_dtable *d_table, uint8_t *d_out);
-/* status of the last dc_huff_decode on this context (synchronising): 0 or DC_E_STREAM */
+/* (5r) random access: decode nranges symbol ranges of the stream: range r = symbols
+ * [d_first[r], d_first[r] + d_count[r]) -> d_out[d_out_off[r] ..), any byte alignment.
+ * d_first / d_count / d_out_off: device u64 arrays, read by the kernels (no host round trip),
+ * so a gather list computed on the GPU can be used as it is. Asynchronous.
+ * The stream arguments are those of dc_huff_decode (d_words 16-B aligned, the same payload slack,
+ * any valid sync_syms, any table; stale decoder tables are rebuilt or reported the same way).
+ * Only the chunks a range touches are read: the payload bits from its first chunk's start to its
+ * last chunk's end, and the index entries of its groups. No byte of d_out outside the requested
+ * ranges is written. Output ranges that overlap are the caller's business: which range's bytes
+ * land there is unspecified. count 0 is legal (writes nothing); nranges 0 returns DC_OK
+ * without a launch. A bad range (first + count > n, or out_off + count > out_cap) writes
+ * nothing and is reported by dc_huff_decode_status as DC_E_ARG; every other range of the call is
+ * still decoded. At most DC_RANGES_MAX ranges per call: the context keeps 16 B of scratch per
+ * range, and one workgroup scans the per-range group counts (time linear in nranges). */
+#define DC_RANGES_MAX (1ull << 28)
+int dc_huff_decode_ranges(dc_ctx *ctx, const uint32_t *d_words, uint64_t bit_base, uint64_t words,
+                          const uint64_t *d_sync_base, const uint16_t *d_sync_len, uint32_t sync_syms,
+                          uint64_t n, const dc_dtable *d_table,
+                          const uint64_t *d_first, const uint64_t *d_count, const uint64_t *d_out_off,
+                          uint64_t nranges, uint8_t *d_out, uint64_t out_cap);
+/* one range given by value (grid sized on the host, no device arrays, no scan launch) into
+ * d_out[0 .. count), any alignment; first + count > n returns DC_E_ARG at once */
+int dc_huff_decode_range(dc_ctx *ctx, const uint32_t *d_words, uint64_t bit_base, uint64_t words,
+                         const uint64_t *d_sync_base, const uint16_t *d_sync_len, uint32_t sync_syms,
+                         uint64_t n, const dc_dtable *d_table,
+                         uint64_t first, uint64_t count, uint8_t *d_out);
+/* status of the last dc_huff_decode / dc_huff_decode_range(s) on this context (synchronising):
+ * DC_E_STREAM for a corrupt stream or stale tables; DC_E_ARG when only a bad range of
+ * dc_huff_decode_ranges was flagged; 0 otherwise */
 int dc_huff_decode_status(dc_ctx *ctx);
 /* chunks of the last S = 64 dc_huff_decode on this context that took the exact redo (codes
  * longer than the 15-bit table, partial or over-long groups); synchronising, diagnostic */

@@ -40,6 +40,23 @@ int dc_huff_compress_host(const uint8_t *in, uint64_t n, int n_ary, const int32_
 int dc_huff_decompress_host(const uint8_t *in, uint64_t m, uint8_t *out, uint64_t cap,
                             uint64_t *out_len);
 int dc_huff_container_info(const uint8_t *in, uint64_t m, uint64_t *n, int *n_ary, uint64_t *bits);
+/* Range reads by the sync index.
+ * dc_huff_range_span: pure host arithmetic (no device): the part of a stream that symbols
+ * [first, first+count) need. out[0] = first group g0, out[1] = last group g1, out[2] = first
+ * payload bit (h_sync_base[g0]), out[3] = end payload bit (h_sync_base[g1+1], or end_bit, the
+ * stream's bit_base + payload bits, for the last group). h_sync_base: the stream's group bases
+ * in host memory. first + count > n or an invalid sync_syms: DC_E_ARG. The stream from group g0
+ * on is itself a stream of dc_gpu.h: bit_base = out[2], the index pointers advanced to group g0
+ * and chunk 64 g0, n - g0 * 64 * sync_syms symbols.
+ * dc_huff_decompress_range_host: symbols [first, first+count) of a DCH1 container in host
+ * memory. Uploads only the code lengths, the index entries of groups g0..g1 and their payload
+ * bytes, and decodes with dc_huff_decode_range. first + count past the container's n: DC_E_ARG;
+ * count > cap: DC_E_CAPACITY. A netstring container returns DC_E_ARG: its index is base64url
+ * text spread over blocks, so it has no random access (decompress it whole). */
+int dc_huff_range_span(uint64_t n, uint32_t sync_syms, const uint64_t *h_sync_base, uint64_t end_bit,
+                       uint64_t first, uint64_t count, uint64_t out[4]);
+int dc_huff_decompress_range_host(const uint8_t *in, uint64_t m, uint64_t first, uint64_t count,
+                                  uint8_t *out, uint64_t cap, uint64_t *out_len);
 
 /* ---- netstring container: the reference's block format (n_ary_huffman.c:1866-1943) -----
  * A sequence of netstrings "<len>:<payload>," (payload <= 32768 bytes, :1826-1827) whose
