@@ -27,6 +27,13 @@ u32 = C.c_uint32
 i32 = C.c_int
 
 
+class HBatch(C.Structure):
+    """dc_hbatch (dc_gpu.h): the device arrays of a Huffman batch."""
+    _fields_ = [("count", u64), ("n_ary", C.c_int32), ("sync_syms", u32), ("d_lens", vp), ("d_mode", vp),
+                ("d_bits", vp), ("d_pay_off", vp), ("d_payload", vp), ("payload_cap", u64), ("d_sync_off", vp),
+                ("d_sync_len", vp), ("sync_cap", u64), ("d_status", vp)]
+
+
 class DcError(RuntimeError):
     NAMES = {-1: "DC_E_ARG", -2: "DC_E_HIP", -3: "DC_E_CODE_TOO_LONG", -4: "DC_E_NOCODE",
              -5: "DC_E_STATE", -6: "DC_E_CAPACITY", -7: "DC_E_STREAM", -8: "DC_E_FALLBACK"}
@@ -115,6 +122,12 @@ def _declare_core(L):
         "dc_huff_decode_ranges": ([vp, P, u64, u64, P, P, u32, u64, P, P, P, P, u64, P, u64], i32),
         "dc_huff_decode_range": ([vp, P, u64, u64, P, P, u32, u64, P, u64, u64, P], i32),
         "dc_huff_decode_status": ([vp], i32),
+        "dc_huff_batch_payload_bound": ([u64, u64], u64),
+        "dc_huff_batch_sync_bound": ([u64, u64, u32], u64),
+        "dc_huff_encode_batch": ([vp, P, P, u64, C.POINTER(HBatch)], i32),
+        "dc_huff_decode_batch": ([vp, C.POINTER(HBatch), P, P, u64], i32),
+        "dc_huff_decode_batch_scatter": ([vp, C.POINTER(HBatch), P, P, P, u64], i32),
+        "dc_huff_batch_status": ([vp], i32),
         "dc_huff_decode_redo_count": ([vp, C.POINTER(u64)], i32),
         "dc_huff_base64url": ([vp, P, u64, u64, P], i32),
         "dc_huff_text_bits": ([i32, i32], i32),

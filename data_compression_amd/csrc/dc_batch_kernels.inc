@@ -1,0 +1,477 @@
+// dc_batch_kernels.inc -- the batched Huffman codec (dc_huff_encode_batch / dc_huff_decode_batch,
+// dc_gpu.h "Huffman batch v1"); included by dc_core.hip after the range decode. Many small
+// independent segments, one code table each, a fixed number of launches for any batch:
+//   k_hb_plan     one workgroup per segment on a persistent grid: the histogram in LDS, the
+//                 lengths and canonical codes by huff_table_body (no dc_dtable written), then the
+//                 compact record: lens (u8 x 256), mode, bits, and the segment's payload bytes
+//                 and sync entries for the scans
+//   k_scan_u64    twice: pay_off and sync_off
+//   k_hb_pack     one workgroup per segment: the codes rebuilt from lens, the bit length of
+//                 every 16-symbol unit (unit u by thread u % 256: neighbouring lanes read
+//                 neighbouring 16 bytes), a workgroup scan, the bits OR-ed into an LDS stage and
+//                 stored as whole 16-B pieces (zero pad included); a stored segment is a padded copy
+//   k_hb_decode   one workgroup per segment: a 12-bit first-level table and the canonical
+//                 arrays from lens; the chunk lengths scanned 256 chunks at a time, chunk c by
+//                 thread c % 256, every chunk checked to decode to exactly its bits, into an LDS
+//                 stage that has the destination's 16-B phase (4 pad bytes per 128: at S = 64 the
+//                 lanes' rows are 16 and 17 dwords apart in turn, two lanes to a bank at worst
+//                 where unpadded rows put sixteen), then written as a byte head, 16-B pieces
+//                 and a byte tail
+// A segment's status goes to status[i]; the lowest failing (index, status) of the call is kept
+// in *first (atomicMin) for dc_huff_batch_status.
+
+#define HB_THREADS 256
+#define HB_UNIT 16                                   /* symbols per pack work unit (divides S)  */
+#define HB_UNITS_MAX (DC_BATCH_SEG_MAX / HB_UNIT)
+#define HB_LUT_BITS 12
+#define HB_NO_FAIL (~0ull)
+
+static __device__ __forceinline__ void hb_fail(int32_t *__restrict__ status, unsigned long long *__restrict__ first,
+                                               uint64_t i, int st)
+{
+    status[i] = st;
+    atomicMin(first, (unsigned long long)((i << 8) | (uint64_t)(uint32_t)(-st)));
+}
+
+static __host__ __device__ __forceinline__ uint32_t hb_pad16(uint32_t bytes) { return (bytes + 15u) & ~15u; }
+
+// ---- plan ---------------------------------------------------------------------------------
+struct HbPlanLds {
+    TblLds tbl;
+    uint64_t h64[256];
+    uint32_t h[256];
+    uint32_t red[4];
+};
+
+__global__ __launch_bounds__(HB_THREADS) void k_hb_plan(const uint8_t *__restrict__ in, const uint64_t *__restrict__ in_off,
+                                                        uint64_t count, int nary, uint32_t S, uint8_t *__restrict__ lens,
+                                                        uint8_t *__restrict__ mode, uint32_t *__restrict__ bits,
+                                                        uint64_t *__restrict__ psize, uint64_t *__restrict__ nchunks,
+                                                        int32_t *__restrict__ status, unsigned long long *__restrict__ first)
+{
+    __shared__ HbPlanLds L;
+    const int t = threadIdx.x;
+    const uint32_t slog = (uint32_t)__builtin_ctz(S);
+    for (uint64_t i = blockIdx.x; i < count; i += gridDim.x) {
+        __syncthreads();   // the LDS of the segment before
+        const uint64_t a = in_off[i], b = in_off[i + 1];
+        if (b < a || b - a > DC_BATCH_SEG_MAX) {   // (workgroup-uniform)
+            if (t == 0) { psize[i] = 0; nchunks[i] = 0; hb_fail(status, first, i, DC_E_ARG); }
+            continue;
+        }
+        const uint32_t len = (uint32_t)(b - a);
+        if (t == 0) status[i] = DC_OK;
+        if (len == 0) {   // stored, 0 bytes
+            lens[i * 256 + t] = 0;
+            if (t == 0) { mode[i] = 0; bits[i] = 0; psize[i] = 0; nchunks[i] = 0; }
+            continue;
+        }
+        L.h[t] = 0;
+        __syncthreads();
+        {   // the histogram: a byte head up to 4-B alignment, dwords, a byte tail (u32 counters:
+            // 65536 equal bytes pass a u16)
+            const uint8_t *p = in + a;
+            const uint32_t mis = (uint32_t)(-(uintptr_t)p) & 3u;
+            const uint32_t head = mis < len ? mis : len;
+            if ((uint32_t)t < head) atomicAdd(&L.h[p[t]], 1u);
+            const uint32_t nw = (len - head) >> 2;
+            const uint32_t *pw = reinterpret_cast<const uint32_t *>(p + head);
+            for (uint32_t k = t; k < nw; k += HB_THREADS) {
+                const uint32_t v = pw[k];
+                atomicAdd(&L.h[v & 255u], 1u);
+                atomicAdd(&L.h[(v >> 8) & 255u], 1u);
+                atomicAdd(&L.h[(v >> 16) & 255u], 1u);
+                atomicAdd(&L.h[v >> 24], 1u);
+            }
+            const uint32_t tail = head + 4 * nw + (uint32_t)t;
+            if (tail < len) atomicAdd(&L.h[p[tail]], 1u);
+        }
+        __syncthreads();
+        L.h64[t] = L.h[t];
+        __syncthreads();
+        // lengths and canonical codes of symbols 0..258 exactly as k_huff_table (dc_huff_table)
+        huff_table_body(L.tbl, L.h64, 1, nullptr, 258, nary, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+        uint32_t v = L.h[t] * L.tbl.nb[t];   // <= 65536 * 32
+#pragma unroll
+        for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
+        if ((t & 63) == 0) L.red[t >> 6] = v;
+        lens[i * 256 + t] = (uint8_t)L.tbl.len[t];
+        __syncthreads();
+        if (t == 0) {
+            const uint32_t cb = L.red[0] + L.red[1] + L.red[2] + L.red[3];
+            const bool huff = !L.tbl.bad && L.tbl.maxbits <= 32 && cb < 8u * len;
+            const uint32_t sb = huff ? cb : 8u * len;
+            mode[i] = huff ? 1 : 0;
+            bits[i] = sb;
+            psize[i] = hb_pad16((sb + 7u) >> 3);
+            nchunks[i] = (len + S - 1) >> slog;
+        }
+    }
+}
+
+// ---- the canonical code of a lens record -----------------------------------------------------
+// (convert_lengths_to_encode_table on lengths 0..255, symbols 256..258 at length 0: the first
+// value per length is n * (first + count) of the length below, u32 wrapping as the table kernel;
+// a symbol's value is its length's first value plus its rank among the symbols of that length)
+struct HbCode {
+    uint32_t code[256];    // packed MSB-first bits (pack)
+    uint32_t nb[256];      // bit length; 0: no code, or a code over 32 bits
+    uint32_t cnt[DC_MAX_DIGITS + 2], startv[DC_MAX_DIGITS + 2], starti[DC_MAX_DIGITS + 2];
+    uint8_t len[256];
+    uint8_t syms[256];     // symbols by (length, value)
+    int mn, mx, bad;       // bad: a length over DC_MAX_DIGITS, or a code over 32 bits
+};
+
+// 256 threads; ends with a barrier
+static __device__ void hb_canonical(HbCode &C, const uint8_t *__restrict__ lens, int nary, int w)
+{
+    const int t = threadIdx.x;
+    const int Lt = lens[t];
+    C.len[t] = (uint8_t)Lt;
+    if (t < DC_MAX_DIGITS + 2) C.cnt[t] = 0;
+    if (t == 0) { C.mn = 300; C.mx = 0; C.bad = 0; }
+    __syncthreads();
+    const bool coded = Lt > 0 && Lt <= DC_MAX_DIGITS;
+    if (Lt > DC_MAX_DIGITS) C.bad = 1;
+    if (coded) { atomicAdd(&C.cnt[Lt], 1u); atomicMin(&C.mn, Lt); atomicMax(&C.mx, Lt); }
+    __syncthreads();
+    if (t == 0) {
+        uint32_t v = 0, si = 0;
+        for (int L = C.mn; L <= C.mx; ++L) {
+            C.startv[L] = v;
+            C.starti[L] = si;
+            v = (v + C.cnt[L]) * (uint32_t)nary;
+            si += C.cnt[L];
+        }
+    }
+    __syncthreads();
+    uint32_t code = 0, nb = 0;
+    if (coded) {
+        uint32_t rank = 0;
+        for (int i = 0; i < t; ++i) rank += (C.len[i] == Lt);   // (an LDS broadcast per step)
+        const uint32_t val = C.startv[Lt] + rank;
+        C.syms[C.starti[Lt] + rank] = (uint8_t)t;
+        if (Lt * w <= 32) {
+            uint64_t packed = 0;
+            if ((nary & (nary - 1)) == 0) {
+                packed = (Lt * w >= 32) ? (uint64_t)val : ((uint64_t)val & ((1ull << (Lt * w)) - 1));
+            } else {
+                uint32_t x = val;
+                for (int d = 0; d < Lt; ++d) {
+                    packed |= (uint64_t)(x % (uint32_t)nary) << (w * d);
+                    x /= (uint32_t)nary;
+                }
+            }
+            code = (uint32_t)packed;
+            nb = (uint32_t)(Lt * w);
+        } else {
+            C.bad = 1;
+        }
+    }
+    C.code[t] = code;
+    C.nb[t] = nb;
+    __syncthreads();
+}
+
+// ---- pack -------------------------------------------------------------------------------------
+struct HbPackLds {
+    __attribute__((aligned(16))) uint32_t stage[DC_BATCH_SEG_MAX / 4];   // the payload, word bit 31 first
+    HbCode C;
+    uint16_t ulen[HB_UNITS_MAX];   // bits per 16-symbol unit
+    uint32_t tbase[HB_THREADS];    // bit offset of unit 16 t
+    uint32_t scan[4];
+};
+static_assert(HB_UNITS_MAX == 16 * HB_THREADS, "the unit scan gives every thread 16 units");
+
+// bytes p[at .. at + 16) of a segment of len bytes (at < len) as 4 little-endian dwords, by
+// aligned dword loads: only dwords that hold a byte of the segment are read; the bytes at and
+// past len are unspecified
+static __device__ __forceinline__ void hb_load16(const uint8_t *__restrict__ p, uint32_t at, uint32_t len, uint32_t q[4])
+{
+    const uint8_t *const s = p + at, *const end = p + len;
+    const uint32_t a = (uint32_t)(uintptr_t)s & 3u;
+    const uint32_t *const w = reinterpret_cast<const uint32_t *>(s - a);
+    uint32_t d[5];
+#pragma unroll
+    for (int j = 0; j < 5; ++j) d[j] = reinterpret_cast<const uint8_t *>(w + j) < end ? w[j] : 0u;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) q[j] = __builtin_amdgcn_alignbyte(d[j + 1], d[j], a);
+}
+
+__global__ __launch_bounds__(HB_THREADS) void k_hb_pack(const uint8_t *__restrict__ in, const uint64_t *__restrict__ in_off,
+                                                        uint64_t count, int nary, int w, uint32_t S,
+                                                        const uint8_t *__restrict__ lens, const uint8_t *__restrict__ mode,
+                                                        const uint64_t *__restrict__ pay_off, uint8_t *__restrict__ payload,
+                                                        uint64_t payload_cap, const uint64_t *__restrict__ sync_off,
+                                                        uint16_t *__restrict__ sync_len, uint64_t sync_cap,
+                                                        int32_t *__restrict__ status, unsigned long long *__restrict__ first)
+{
+    __shared__ HbPackLds L;
+    const int t = threadIdx.x;
+    const uint32_t slog = (uint32_t)__builtin_ctz(S);
+    for (uint64_t i = blockIdx.x; i < count; i += gridDim.x) {
+        __syncthreads();   // the LDS of the segment before
+        if (status[i] != DC_OK) continue;   // (DC_E_ARG by the plan; uniform)
+        const uint64_t a = in_off[i];
+        const uint32_t len = (uint32_t)(in_off[i + 1] - a);
+        const uint64_t po = pay_off[i], pe = pay_off[i + 1], so = sync_off[i], se = sync_off[i + 1];
+        if (pe > payload_cap || se > sync_cap) {
+            if (t == 0) hb_fail(status, first, i, DC_E_CAPACITY);
+            continue;
+        }
+        if (len == 0) continue;
+        const uint32_t psz = (uint32_t)(pe - po), nch = (uint32_t)(se - so);
+        const uint8_t *p = in + a;
+        uint4 *const dst = reinterpret_cast<uint4 *>(payload + po);   // (po and payload 16-B aligned)
+        if (mode[i] == 0) {   // stored: the bytes, zero-padded to 16
+            for (uint32_t v = t; v < psz / 16; v += HB_THREADS) {
+                uint32_t q[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    uint32_t x = 0;
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        const uint32_t at = 16 * v + 4 * j + k;
+                        if (at < len) x |= (uint32_t)p[at] << (8 * k);
+                    }
+                    q[j] = x;
+                }
+                dst[v] = make_uint4(q[0], q[1], q[2], q[3]);
+            }
+            for (uint32_t c = t; c < nch; c += HB_THREADS) {
+                const uint32_t left = len - (c << slog);
+                sync_len[so + c] = (uint16_t)(8u * (left < S ? left : S));
+            }
+            continue;
+        }
+        hb_canonical(L.C, lens + i * 256, nary, w);
+        for (uint32_t k = t; k < psz / 4; k += HB_THREADS) L.stage[k] = 0;
+        // unit u (16 symbols) by thread u % 256: its bit length, then the scan (thread t sums
+        // units 16 t .. 16 t + 15), then its codes OR-ed into the stage at its bit offset
+        const uint32_t units = (len + HB_UNIT - 1) / HB_UNIT;
+        for (uint32_t u = t; u < units; u += HB_THREADS) {
+            uint32_t q[4];
+            hb_load16(p, u * HB_UNIT, len, q);
+            const uint32_t cntu = min((uint32_t)HB_UNIT, len - u * HB_UNIT);
+            uint32_t ub = 0;
+#pragma unroll
+            for (uint32_t k = 0; k < HB_UNIT; ++k)
+                if (k < cntu) ub += L.C.nb[(q[k >> 2] >> (8 * (k & 3))) & 255u];
+            L.ulen[u] = (uint16_t)ub;   // <= 16 * 32
+        }
+        __syncthreads();
+        uint32_t tsum = 0;
+        for (uint32_t u = 16 * (uint32_t)t; u < min(16 * (uint32_t)t + 16, units); ++u) tsum += L.ulen[u];
+        uint32_t total;
+        L.tbase[t] = wg_scan_excl_u32(tsum, L.scan, &total);
+        __syncthreads();
+        {   // the sync index: chunk c = units [c r, (c + 1) r), r = S / 16
+            const uint32_t r = S / HB_UNIT;
+            for (uint32_t c = t; c < nch; c += HB_THREADS) {
+                const uint32_t e = min((c + 1) * r, units);
+                uint32_t cb = 0;
+                for (uint32_t u = c * r; u < e; ++u) cb += L.ulen[u];
+                sync_len[so + c] = (uint16_t)cb;   // <= 1024 * 32
+            }
+        }
+        for (uint32_t u = t; u < units; u += HB_THREADS) {
+            uint32_t pos = L.tbase[u >> 4];
+            for (uint32_t k = u & ~15u; k < u; ++k) pos += L.ulen[k];
+            uint32_t q[4];
+            hb_load16(p, u * HB_UNIT, len, q);
+            const uint32_t cntu = min((uint32_t)HB_UNIT, len - u * HB_UNIT);
+            // a 64-bit accumulator, whole words OR-ed into the stage (neighbours share words)
+            uint32_t wi = pos >> 5, nacc = pos & 31u;
+            uint64_t acc = 0;
+#pragma unroll
+            for (uint32_t k = 0; k < HB_UNIT; ++k) {
+                if (k < cntu) {
+                    const uint32_t b = (q[k >> 2] >> (8 * (k & 3))) & 255u, nb = L.C.nb[b];
+                    if (nb) acc |= (uint64_t)L.C.code[b] << (64u - nacc - nb);
+                    nacc += nb;
+                    if (nacc >= 32u) {
+                        if (wi < DC_BATCH_SEG_MAX / 4) atomicOr(&L.stage[wi], (uint32_t)(acc >> 32));
+                        ++wi;
+                        acc <<= 32;
+                        nacc -= 32u;
+                    }
+                }
+            }
+            if (nacc && wi < DC_BATCH_SEG_MAX / 4) atomicOr(&L.stage[wi], (uint32_t)(acc >> 32));
+        }
+        __syncthreads();
+        for (uint32_t v = t; v < psz / 16; v += HB_THREADS) {
+            const uint4 q = reinterpret_cast<const uint4 *>(L.stage)[v];
+            dst[v] = make_uint4(bswap32(q.x), bswap32(q.y), bswap32(q.z), bswap32(q.w));
+        }
+    }
+}
+
+// ---- decode -----------------------------------------------------------------------------------
+struct HbDecLds {
+    // byte k of the segment at out[HB_OIDX(phase + k)]: 4 pad bytes after every 128
+    __attribute__((aligned(16))) uint8_t out[DC_BATCH_SEG_MAX + 16 + 4 * (DC_BATCH_SEG_MAX / 128 + 1)];
+    uint16_t lut[1 << HB_LUT_BITS];   // next 12 bits -> sym | bits << 8; 0: longer, or no code
+    HbCode C;
+    uint32_t scan[4];
+    int bad;
+};
+
+#define HB_OIDX(pos) ((pos) + 4u * ((pos) >> 7))
+
+// the symbol whose code leads the 32-bit window `win` (MSB first), by the canonical arrays:
+// its bit length, 0 when no code of lo .. maxbits bits matches (lo: bits the caller has ruled out
+// already are not tested again)
+static __device__ __forceinline__ uint32_t hb_decode_slow(uint32_t win, uint32_t lo, uint32_t maxbits, const HbCode &C,
+                                                          int nary, int w, uint32_t &sym)
+{
+    const int top = C.mx;
+    if ((nary & (nary - 1)) == 0) {   // n = 2^w: the value of the first L digits is the first L w bits
+        int L = C.mn;
+        while ((uint32_t)(L * w) < lo) ++L;
+        for (; L <= top && (uint32_t)(L * w) <= maxbits; ++L) {
+            const uint32_t r = (win >> (32 - L * w)) - C.startv[L];
+            if (r < C.cnt[L]) {
+                sym = C.syms[C.starti[L] + r];
+                return (uint32_t)(L * w);
+            }
+        }
+        return 0;
+    }
+    uint32_t v = 0;
+    const uint32_t dmask = (1u << w) - 1u;
+    for (int L = 1; L <= top && (uint32_t)(L * w) <= maxbits; ++L) {
+        const uint32_t d = (win >> (32 - L * w)) & dmask;
+        if (d >= (uint32_t)nary) return 0;
+        v = v * (uint32_t)nary + d;
+        if (L >= C.mn && (uint32_t)(L * w) >= lo) {
+            const uint32_t r = v - C.startv[L];
+            if (r < C.cnt[L]) {
+                sym = C.syms[C.starti[L] + r];
+                return (uint32_t)(L * w);
+            }
+        }
+    }
+    return 0;
+}
+
+__global__ __launch_bounds__(HB_THREADS) void k_hb_decode(uint64_t count, int nary, int w, uint32_t S,
+                                                          const uint8_t *__restrict__ lens, const uint8_t *__restrict__ mode,
+                                                          const uint32_t *__restrict__ bits, const uint64_t *__restrict__ pay_off,
+                                                          const uint8_t *__restrict__ payload, uint64_t payload_cap,
+                                                          const uint64_t *__restrict__ sync_off,
+                                                          const uint16_t *__restrict__ sync_len, uint64_t sync_cap,
+                                                          uint8_t *__restrict__ out, const uint64_t *out_beg, const uint64_t *out_end,
+                                                          uint64_t out_cap, int32_t *__restrict__ status,
+                                                          unsigned long long *__restrict__ first)
+{
+    __shared__ HbDecLds L;
+    const int t = threadIdx.x;
+    const uint32_t slog = (uint32_t)__builtin_ctz(S);
+    for (uint64_t i = blockIdx.x; i < count; i += gridDim.x) {
+        __syncthreads();   // the LDS of the segment before
+        const uint64_t oa = out_beg[i], ob = out_end[i];   // (the two may alias: d_out_off, d_out_off + 1)
+        if (ob < oa || ob - oa > DC_BATCH_SEG_MAX) {   // (every test here is workgroup-uniform)
+            if (t == 0) hb_fail(status, first, i, DC_E_ARG);
+            continue;
+        }
+        if (ob > out_cap) {
+            if (t == 0) hb_fail(status, first, i, DC_E_CAPACITY);
+            continue;
+        }
+        const uint32_t len = (uint32_t)(ob - oa);
+        const uint32_t md = mode[i], sb = bits[i];
+        const uint64_t po = pay_off[i], pe = pay_off[i + 1], so = sync_off[i], se = sync_off[i + 1];
+        const uint32_t nch = (len + S - 1) >> slog;
+        bool ok = md <= 1u && sb <= 8u * len && (md == 1u || sb == 8u * len);
+        ok = ok && pe >= po && pe <= payload_cap && (po & 15u) == 0 && pe - po == hb_pad16((sb + 7u) >> 3);
+        ok = ok && se >= so && se <= sync_cap && se - so == nch;
+        if (!ok) {
+            if (t == 0) hb_fail(status, first, i, DC_E_STREAM);
+            continue;
+        }
+        if (t == 0) { status[i] = DC_OK; L.bad = 0; }
+        if (len == 0) continue;
+        uint8_t *const dptr = out + oa;
+        const uint32_t phase = (uint32_t)(uintptr_t)dptr & 15u;
+        const uint8_t *const pay = payload + po;
+        // chunk c by thread c % 256, 256 chunks at a time: their bit lengths scanned in the
+        // workgroup, then decoded (every barrier below is reached by the whole workgroup)
+        if (md == 1u) {
+            hb_canonical(L.C, lens + i * 256, nary, w);
+            if (L.C.bad) {   // (uniform: read after hb_canonical's barrier)
+                if (t == 0) hb_fail(status, first, i, DC_E_STREAM);
+                continue;
+            }
+            for (uint32_t e = t; e < (1u << HB_LUT_BITS); e += HB_THREADS) {
+                uint32_t sym = 0;
+                const uint32_t nb = hb_decode_slow(e << (32 - HB_LUT_BITS), 1u, HB_LUT_BITS, L.C, nary, w, sym);
+                L.lut[e] = (uint16_t)(nb ? (sym | (nb << 8)) : 0u);
+            }
+            __syncthreads();
+        } else {
+            for (uint32_t k = t; k < len; k += HB_THREADS) L.out[HB_OIDX(phase + k)] = pay[k];
+        }
+        const uint32_t nw = (uint32_t)(pe - po) / 4;
+        const uint32_t *const pw = reinterpret_cast<const uint32_t *>(pay);
+#define HB_WORD(k) ((k) < nw ? bswap32(pw[k]) : 0u)
+        uint32_t base = 0;
+        int bad = 0;
+        for (uint32_t c0 = 0; c0 < nch; c0 += HB_THREADS) {
+            const uint32_t c = c0 + (uint32_t)t;
+            const uint32_t clen = c < nch ? sync_len[so + c] : 0u;
+            uint32_t tot;
+            const uint32_t pos = base + wg_scan_excl_u32(clen, L.scan, &tot);
+            base += tot;
+            if (c >= nch || bad) continue;
+            const uint32_t sym0 = c << slog;
+            const uint32_t cnt = min(S, len - sym0);
+            if (md == 0) {   // stored: 8 bits a symbol
+                bad |= clen != 8u * cnt;
+                continue;
+            }
+            uint32_t k = pos >> 5;
+            const uint32_t sh = pos & 31u;
+            uint64_t win = (((uint64_t)HB_WORD(k) << 32) | HB_WORD(k + 1)) << sh;
+            int wbits = 64 - (int)sh;
+            k += 2;
+            uint32_t used = 0;
+            const uint32_t row = phase + sym0;
+            for (uint32_t j = 0; j < cnt; ++j) {
+                if (wbits < 32) {
+                    win |= (uint64_t)HB_WORD(k) << (32 - wbits);
+                    ++k;
+                    wbits += 32;
+                }
+                const uint32_t e = L.lut[win >> (64 - HB_LUT_BITS)];
+                uint32_t nb = e >> 8, sym = e & 255u;
+                if (!nb) {
+                    nb = hb_decode_slow((uint32_t)(win >> 32), HB_LUT_BITS + 1u, 32u, L.C, nary, w, sym);
+                    if (!nb) { bad = 1; break; }
+                }
+                L.out[HB_OIDX(row + j)] = (uint8_t)sym;
+                win <<= nb;
+                wbits -= (int)nb;
+                used += nb;
+            }
+            if (used != clen) bad = 1;
+        }
+#undef HB_WORD
+        if (bad || base != sb) L.bad = 1;   // (base: the chunk lengths must sum to bits)
+        __syncthreads();
+        if (L.bad) {   // nothing of a corrupt segment is written
+            if (t == 0) hb_fail(status, first, i, DC_E_STREAM);
+            continue;
+        }
+        // the stage has the destination's 16-B phase: a byte head, aligned 16-B pieces, a byte tail
+        const uint32_t head = min((16u - phase) & 15u, len);
+        if ((uint32_t)t < head) dptr[t] = L.out[HB_OIDX(phase + t)];
+        const uint32_t nbody = (len - head) >> 4;
+        for (uint32_t v = t; v < nbody; v += HB_THREADS) {   // (a piece never crosses a pad: 16 divides 128)
+            const uint32_t *const q = reinterpret_cast<const uint32_t *>(L.out + HB_OIDX(phase + head + 16 * v));
+            *reinterpret_cast<uint4 *>(dptr + head + 16 * v) = make_uint4(q[0], q[1], q[2], q[3]);
+        }
+        const uint32_t tail = head + 16 * nbody + (uint32_t)t;
+        if (tail < len) dptr[tail] = L.out[HB_OIDX(phase + tail)];
+    }
+}

@@ -17,6 +17,7 @@
 #include <type_traits>
 
 #include "dc_gpu.h"
+#include "dc_batch_bound.h"
 
 #define DC_VERSION "dc-mi355x 0.1 (gfx950)"
 #define DC_SYNC_GROUP 64
@@ -803,15 +804,17 @@ static __device__ void huff_table_body(TblLds &S, const uint64_t *__restrict__ f
         // canonical rank = symbols of the same length before this one (index order)
         const int L = s_len[i];
         const bool coded = L >= minL && L <= topL;
-        T->lengths[i] = L;
+        if (T) T->lengths[i] = L;
         if (coded) {
             const uint32_t *mk = s_mask + (L - 1) * MW;
             uint32_t rank = (uint32_t)__popc(mk[i >> 5] & ((1u << (i & 31)) - 1u));
             for (int q = 0; q < (i >> 5); ++q) rank += (uint32_t)__popc(mk[q]);
             const uint32_t val = s_startv[L] + rank;
-            T->enc_len[i] = L;
-            T->enc_val[i] = val;
-            T->syms[s_starti[L] + rank] = (uint16_t)i;
+            if (T) {
+                T->enc_len[i] = L;
+                T->enc_val[i] = val;
+                T->syms[s_starti[L] + rank] = (uint16_t)i;
+            }
             if (i < 256) {
                 // L base-n digits of val, MSB-first, w bits each (n = 2^w: the bits of val)
                 if ((long long)L * w <= 32) {
@@ -832,16 +835,18 @@ static __device__ void huff_table_body(TblLds &S, const uint64_t *__restrict__ f
                     atomicMax(&s_maxbits, 33);
                 }
             }
-            if (i == M) T->last_written = 1;
-        } else {
+            if (T && i == M) T->last_written = 1;
+        } else if (T) {
             if (i < M) { T->enc_len[i] = 0; T->enc_val[i] = 0; }
             else { T->last_written = 0; T->enc_len[i] = 0; T->enc_val[i] = 0; }
         }
     }
-    for (int i = leaves + t; i < DC_MAX_SYMS; i += 256) {
+    // T == nullptr (the batch plan, dc_batch_kernels.inc): no dc_dtable is written; the caller
+    // reads the lengths, codes and flags from S (len, code, nb, maxbits, bad) after the barrier
+    for (int i = leaves + t; T && i < DC_MAX_SYMS; i += 256) {
         T->lengths[i] = 0; T->enc_len[i] = 0; T->enc_val[i] = 0;
     }
-    for (int L = t; L <= DC_MAX_DIGITS; L += 256) {
+    for (int L = t; T && L <= DC_MAX_DIGITS; L += 256) {
         const bool in = (L >= minL && L <= maxL);
         T->first[L] = in ? s_startv[L] : 0u;
         T->count[L] = in ? s_cnt[L] : 0u;
@@ -849,7 +854,7 @@ static __device__ void huff_table_body(TblLds &S, const uint64_t *__restrict__ f
     }
     // left-justified canonical limits per BIT length b (power-of-two n): codes of digit
     // length <= floor(b/w) are exactly the 32-bit windows below lim[b]
-    if (t <= 32) {
+    if (T && t <= 32) {
         const int Ld = t / w;
         uint64_t lim;
         if (Ld < minL) lim = 0;
@@ -858,6 +863,7 @@ static __device__ void huff_table_body(TblLds &S, const uint64_t *__restrict__ f
         T->lim[t] = lim;
     }
     __syncthreads();   // s_code, s_nb, s_maxbits
+    if (!T) return;    // (workgroup-uniform)
     T->code[t] = s_code[t];
     T->nbits[t] = s_nb[t];
     // every coded byte 8 bits long (n = 16 on a flat byte distribution: a full depth-2 tree):
@@ -6260,6 +6266,7 @@ __global__ __launch_bounds__(256) void k_copy_probe(const uint4 *__restrict__ sr
 }
 
 #include "dc_range_kernels.inc"
+#include "dc_batch_kernels.inc"
 
 #ifdef DC_AB_KERNELS
 #include "dc_ab_kernels.inc"
@@ -6292,6 +6299,7 @@ struct dc_ctx {
     uint32_t *d_fixpos;     size_t fixpos_cap;    // decode redo: bit offset of a flagged chunk
     uint64_t last_groups;                         // groups of the last S = 64 decode (redo mask length)
     uint64_t *d_rng;        size_t rng_cap;       // range decode: items per range, then their offsets (+ total)
+    uint64_t *d_hb;         size_t hb_cap;        // batch codec: first failure, then payload bytes and chunks per segment
     uint64_t *d_hloc;                             // this context's last histogram (256 u64; hist[] may be all-reduced)
     const dc_dtable *plan_table;                  // the table and device total of the last plan
     uint64_t *plan_total;
@@ -6320,6 +6328,7 @@ struct dc_ctx {
     uint32_t opt_hist_grid;       // histogram workgroups (0: default 512)
     uint32_t opt_pack_grid;       // pack: workgroups of k_huff_pack (0: a block pair each; A/B builds: blocks per wave of k_huff_pack_w)
     uint32_t opt_pack_block;      // 2/3: the wave-per-range pack (k_huff_pack_w; 3: 4 codes a lane), A/B
+    uint32_t opt_batch_grid;      // batch codec: workgroups of its kernels (0: what the device holds at once)
     uint32_t opt_nyb_wtile_off;   // 1: the nybble encode / decode write with k_fsm_write (A/B, parity tests)
     uint32_t opt_d8_static;       // decoder: static share of the tuples, percent (0..100)
     uint32_t opt_decode_general;  // 1: always the general decoder (k_huff_decode)
@@ -6477,6 +6486,7 @@ void dc_ctx_destroy(dc_ctx *c)
     if (c->d_fix) (void)hipFree(c->d_fix);
     if (c->d_fixpos) (void)hipFree(c->d_fixpos);
     if (c->d_rng) (void)hipFree(c->d_rng);
+    if (c->d_hb) (void)hipFree(c->d_hb);
     if (c->d_scr) (void)hipFree(c->d_scr);
     if (c->d_meta) (void)hipFree(c->d_meta);
     if (c->d_summ) (void)hipFree(c->d_summ);
@@ -6549,6 +6559,10 @@ int dc_ctx_set_option(dc_ctx *c, int option, int64_t value)
     case DC_OPT_NYB_WTILE_OFF:
         if (value != 0 && value != 1) return DC_E_ARG;
         c->opt_nyb_wtile_off = (uint32_t)value;
+        return DC_OK;
+    case DC_OPT_BATCH_GRID:
+        if (value < 0 || value > 65536) return DC_E_ARG;
+        c->opt_batch_grid = (uint32_t)value;
         return DC_OK;
     default:
         return DC_E_ARG;
@@ -7237,6 +7251,92 @@ int dc_huff_decode_range(dc_ctx *c, const uint32_t *d_words, uint64_t bit_base, 
            d_sync_len, S, n, d_table, (const uint64_t *)nullptr, (const uint64_t *)nullptr, (const uint64_t *)nullptr,
            (const uint64_t *)nullptr, (uint64_t)1, first, count, d_out, derr, derr_next);
     return DC_OK;
+}
+
+// the batched codec (dc_batch_kernels.inc)
+uint64_t dc_huff_batch_payload_bound(uint64_t total_bytes, uint64_t count)
+{
+    return dc_batch_payload_bound_calc(total_bytes, count);
+}
+uint64_t dc_huff_batch_sync_bound(uint64_t total_bytes, uint64_t count, uint32_t S)
+{
+    return dc_batch_sync_bound_calc(total_bytes, count, S);
+}
+
+static int hbatch_args(dc_ctx *c, const dc_hbatch *b)
+{
+    if (!c || !b) return DC_E_ARG;
+    if (b->n_ary < 2 || b->n_ary > 256 || !sync_ok(b->sync_syms)) return DC_E_ARG;
+    if (b->count == 0) return DC_OK;
+    if (!b->d_lens || !b->d_mode || !b->d_bits || !b->d_pay_off || !b->d_sync_off || !b->d_status) return DC_E_ARG;
+    if ((!b->d_payload && b->payload_cap) || (!b->d_sync_len && b->sync_cap)) return DC_E_ARG;
+    if (((uintptr_t)b->d_payload) & 15) return DC_E_ARG;
+    return DC_OK;
+}
+
+static int hbatch_w(int nary)
+{
+    int w = 0;
+    while ((1 << w) < nary) ++w;
+    return w;
+}
+
+int dc_huff_encode_batch(dc_ctx *c, const uint8_t *d_in, const uint64_t *d_in_off, uint64_t count, const dc_hbatch *b)
+{
+    if (const int r = hbatch_args(c, b)) return r;
+    if (b->count != count) return DC_E_ARG;
+    if (count == 0) return DC_OK;
+    if (!d_in_off || count > DC_RANGES_MAX) return DC_E_ARG;
+    if (ensure((void **)&c->d_hb, &c->hb_cap, (2 * count + 2) * sizeof(uint64_t))) return DC_E_HIP;
+    unsigned long long *const first = reinterpret_cast<unsigned long long *>(c->d_hb);
+    uint64_t *const psize = c->d_hb + 2, *const nch = c->d_hb + 2 + count;
+    HIPCHK(hipMemsetAsync(first, 0xFF, sizeof(uint64_t), c->stream));
+    // persistent grids: the workgroups a 256-CU device holds at once (LDS-bound: 3 and 2 per CU)
+    const uint64_t cap3 = c->opt_batch_grid ? c->opt_batch_grid : 768, cap2 = c->opt_batch_grid ? c->opt_batch_grid : 512;
+    const uint64_t g3 = count < cap3 ? count : cap3, g2 = count < cap2 ? count : cap2;
+    LAUNCH(c, "hb_plan", k_hb_plan, g3, HB_THREADS, d_in, d_in_off, count, (int)b->n_ary, b->sync_syms, b->d_lens, b->d_mode,
+           b->d_bits, psize, nch, b->d_status, first);
+    LAUNCH(c, "hb_scan_pay", k_scan_u64, 1, 1024, (const uint64_t *)psize, count, b->d_pay_off);
+    LAUNCH(c, "hb_scan_sync", k_scan_u64, 1, 1024, (const uint64_t *)nch, count, b->d_sync_off);
+    LAUNCH(c, "hb_pack", k_hb_pack, g2, HB_THREADS, d_in, d_in_off, count, (int)b->n_ary, hbatch_w(b->n_ary), b->sync_syms,
+           (const uint8_t *)b->d_lens, (const uint8_t *)b->d_mode, (const uint64_t *)b->d_pay_off, b->d_payload,
+           b->payload_cap, (const uint64_t *)b->d_sync_off, b->d_sync_len, b->sync_cap, b->d_status, first);
+    return DC_OK;
+}
+
+int dc_huff_decode_batch_scatter(dc_ctx *c, const dc_hbatch *b, uint8_t *d_out, const uint64_t *d_out_beg,
+                                 const uint64_t *d_out_end, uint64_t out_cap)
+{
+    if (const int r = hbatch_args(c, b)) return r;
+    const uint64_t count = b->count;
+    if (count == 0) return DC_OK;
+    if (!d_out_beg || !d_out_end || (!d_out && out_cap) || count > DC_RANGES_MAX) return DC_E_ARG;
+    if (ensure((void **)&c->d_hb, &c->hb_cap, (2 * count + 2) * sizeof(uint64_t))) return DC_E_HIP;
+    unsigned long long *const first = reinterpret_cast<unsigned long long *>(c->d_hb);
+    HIPCHK(hipMemsetAsync(first, 0xFF, sizeof(uint64_t), c->stream));
+    const uint64_t cap2 = c->opt_batch_grid ? c->opt_batch_grid : 512;
+    const uint64_t g2 = count < cap2 ? count : cap2;
+    LAUNCH(c, "hb_decode", k_hb_decode, g2, HB_THREADS, count, (int)b->n_ary, hbatch_w(b->n_ary), b->sync_syms,
+           (const uint8_t *)b->d_lens, (const uint8_t *)b->d_mode, (const uint32_t *)b->d_bits,
+           (const uint64_t *)b->d_pay_off, (const uint8_t *)b->d_payload, b->payload_cap, (const uint64_t *)b->d_sync_off,
+           (const uint16_t *)b->d_sync_len, b->sync_cap, d_out, d_out_beg, d_out_end, out_cap, b->d_status, first);
+    return DC_OK;
+}
+
+int dc_huff_decode_batch(dc_ctx *c, const dc_hbatch *b, uint8_t *d_out, const uint64_t *d_out_off, uint64_t out_cap)
+{
+    if (b && b->count && !d_out_off) return DC_E_ARG;
+    return dc_huff_decode_batch_scatter(c, b, d_out, d_out_off, d_out_off + 1, out_cap);
+}
+
+int dc_huff_batch_status(dc_ctx *c)
+{
+    if (!c) return DC_E_ARG;
+    if (!c->d_hb) return DC_OK;   // no batch call yet
+    uint64_t v = 0;
+    HIPCHK(hipMemcpyAsync(&v, c->d_hb, sizeof(v), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return v == HB_NO_FAIL ? DC_OK : -(int)(v & 255u);
 }
 
 int dc_huff_text_bits(int format, int n_ary) { return text_bits(format, n_ary); }

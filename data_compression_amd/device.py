@@ -76,7 +76,7 @@ class Codec:
         check("dc_ctx_set_timing", self.L.dc_ctx_set_timing(self.ctx, int(enable)))
 
     OPTIONS = {"hist_grid": 1, "pack_grid": 2, "decode_static_pct": 3, "decode_general": 4, "hist_prefetch": 5,
-               "decode_variant": 6, "nyb_adec_v1": 7, "pack_block": 8, "nyb_wtile_off": 9}
+               "decode_variant": 6, "nyb_adec_v1": 7, "pack_block": 8, "nyb_wtile_off": 9, "batch_grid": 10}
 
     def set_option(self, name, value: int):
         """dc_ctx_set_option (dc_gpu.h DC_OPT_*): tuning knobs of this context."""
@@ -520,6 +520,96 @@ class Codec:
         check("dc_huff_decode_ranges", self.L.dc_huff_decode_ranges(self.ctx, *stream, _ptr(first), _ptr(count),
                                                                     _ptr(out_off), nr, _ptr(buf), out.numel()))
         return out, out_off
+
+    # ---- batched codec: many small buffers, one table each (dc_gpu.h "Huffman batch v1") ---------
+    SEG_MAX = 65536   # DC_BATCH_SEG_MAX
+
+    def batch_bounds(self, total_bytes: int, count: int, sync_syms: int):
+        """(payload bytes, u16 sync entries) that always hold a batch (dc_huff_batch_*_bound)."""
+        return (int(self.L.dc_huff_batch_payload_bound(total_bytes, count)),
+                int(self.L.dc_huff_batch_sync_bound(total_bytes, count, sync_syms)))
+
+    @staticmethod
+    def _hbatch(enc, payload_cap=None, sync_cap=None):
+        from ._lib import HBatch
+        pcap = enc["payload"].numel() if payload_cap is None else min(int(payload_cap), enc["payload"].numel())
+        scap = enc["sync_len"].numel() if sync_cap is None else min(int(sync_cap), enc["sync_len"].numel())
+        return HBatch(enc["count"], enc["n_ary"], enc["S"], _ptr(enc["lens"]), _ptr(enc["mode"]), _ptr(enc["bits"]),
+                      _ptr(enc["pay_off"]), _ptr(enc["payload"]), pcap, _ptr(enc["sync_off"]), _ptr(enc["sync_len"]),
+                      scap, _ptr(enc["status"]))
+
+    def _i64(self, v, n, name):
+        if not hasattr(v, "data_ptr"):
+            v = torch.from_numpy(np.ascontiguousarray(v, dtype=np.int64).reshape(-1)).to(f"cuda:{self.device}")
+        if v.dtype != torch.int64 or not v.is_cuda or not v.is_contiguous() or v.numel() not in n:
+            raise ValueError(f"{name}: a contiguous int64 device tensor of {' or '.join(map(str, n))} entries")
+        return v
+
+    def encode_batch(self, x, offsets, n_ary: int = 2, sync_syms: int = 64, payload=None, sync_len=None,
+                     payload_cap=None, sync_cap=None):
+        """dc_huff_encode_batch: segment i = x[offsets[i]:offsets[i+1]] (device uint8 x, int64
+        offsets of count + 1 entries, any alignment, each segment <= 65536 bytes) coded under a
+        table of its own, or stored when that is not smaller. Asynchronous, no host read; the
+        launches do not depend on count. Returns a dict of device tensors: lens (count x 256
+        u8), mode, bits, pay_off, payload, sync_off, sync_len, status (per segment; see
+        batch_status()). payload / sync_len: optional preallocated buffers (else sized by
+        batch_bounds); payload_cap / sync_cap: smaller caps to hand to the kernels."""
+        if x.dtype != torch.uint8 or not x.is_contiguous():
+            raise ValueError("encode_batch input: contiguous uint8")
+        offsets = self._i64(offsets, range(1, 1 << 62), "encode_batch offsets")
+        count = offsets.numel() - 1
+        pb, sb = self.batch_bounds(x.numel(), count, sync_syms)
+        payload = payload if payload is not None else self._t(max(pb, 16))
+        sync_len = sync_len if sync_len is not None else self._t(max(sb, 1), torch.int16)
+        enc = {"count": count, "n_ary": n_ary, "S": sync_syms, "offsets": offsets, "total": x.numel(),
+               "lens": self._t(max(count, 1) * 256).view(max(count, 1), 256)[:count], "mode": self._t(max(count, 1))[:count],
+               "bits": self._t(max(count, 1), torch.int32)[:count], "pay_off": self._t(count + 1, torch.int64),
+               "payload": payload, "sync_off": self._t(count + 1, torch.int64), "sync_len": sync_len,
+               "status": self._t(max(count, 1), torch.int32)[:count]}
+        b = self._hbatch(enc, payload_cap, sync_cap)
+        enc["payload_cap"], enc["sync_cap"] = int(b.payload_cap), int(b.sync_cap)
+        check("dc_huff_encode_batch", self.L.dc_huff_encode_batch(self.ctx, _ptr(x), _ptr(offsets), count, C.byref(b)))
+        return enc
+
+    def encode_blocks(self, x, block: int = 65536, **kw):
+        """encode_batch of x cut into independent blocks of `block` bytes (the last shorter),
+        a table each: the reference's own block design (n_ary_huffman.c:1210-1255)."""
+        if not 0 < block <= self.SEG_MAX:
+            raise ValueError("encode_blocks: 0 < block <= 65536")
+        n = x.numel()
+        off = torch.arange(0, n + block, block, dtype=torch.int64, device=x.device).clamp_(max=n)
+        return self.encode_batch(x, off[: (n + block - 1) // block + 1].contiguous(), **kw)
+
+    def decode_batch(self, enc, out=None, out_off=None):
+        """dc_huff_decode_batch of the dict encode_batch returned. out_off (int64 device tensor
+        or sequence): count + 1 entries put segment i at out[out_off[i]:out_off[i+1]]; count
+        entries give each segment's start alone (its length is the encoded segment's), so the
+        outputs may lie anywhere in out (dc_huff_decode_batch_scatter). Default: the segments
+        back to back from 0. Asynchronous; returns (out, out_off). Per-segment outcome in
+        enc["status"], the first failure by batch_status()."""
+        count = enc["count"]
+        if out_off is None:
+            out_off = enc["offsets"] - enc["offsets"][:1]
+        out_off = self._i64(out_off, (count, count + 1), "decode_batch out_off")
+        if out is None:
+            out = self._t(max(enc["total"], 1))[: enc["total"]] if out_off.numel() == count + 1 else None
+            if out is None:
+                raise ValueError("decode_batch: segment starts alone need an output buffer")
+        buf = self._u8_out(out, "decode_batch")
+        b = self._hbatch(enc, enc["payload_cap"], enc["sync_cap"])
+        if out_off.numel() == count + 1:
+            check("dc_huff_decode_batch", self.L.dc_huff_decode_batch(self.ctx, C.byref(b), _ptr(buf), _ptr(out_off),
+                                                                      buf.numel()))
+        else:
+            end = out_off + (enc["offsets"][1:] - enc["offsets"][:-1])
+            check("dc_huff_decode_batch_scatter", self.L.dc_huff_decode_batch_scatter(
+                self.ctx, C.byref(b), _ptr(buf), _ptr(out_off), _ptr(end), buf.numel()))
+        return out, out_off
+
+    def batch_status(self) -> int:
+        """0, or the status of the lowest-numbered failing segment of the last encode_batch /
+        decode_batch on this codec (synchronising)."""
+        return int(self.L.dc_huff_batch_status(self.ctx))
 
     # ---- C5 fused front-end encode (small_compression.c front-end, then Huffman; one pass) -----
     def small_huff_plan(self, x, n_ary: int = 16, max_symbol_value: int = 258, hist=None, table=None, total=None):

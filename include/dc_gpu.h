@@ -133,9 +133,11 @@ enum {
                                      DESIGN.md 'Round 6'): 4 the block by LDS-DMA, 5 half-block
                                      stages, 6 one table read per byte (fold), 7 the next block's
                                      loads issued as pass B frees each piece */
-    DC_OPT_NYB_WTILE_OFF = 9      /* 1: the static nybble encode and the nybble decode write each
+    DC_OPT_NYB_WTILE_OFF = 9,     /* 1: the static nybble encode and the nybble decode write each
                                      4096-element tile with a workgroup (k_fsm_write) instead of a
                                      wave (k_nyb_enc_wtile / k_nyb_dec_wtile) */
+    DC_OPT_BATCH_GRID = 10        /* batch codec: workgroups of its persistent kernels, 0 = what a
+                                     256-CU device holds at once (768 plan, 512 pack / decode) */
 };
 int dc_ctx_set_option(dc_ctx *ctx, int option, int64_t value);
 const char *dc_version(void);
@@ -326,6 +328,84 @@ int dc_huff_decode_status(dc_ctx *ctx);
 /* chunks of the last S = 64 dc_huff_decode on this context that took the exact redo (codes
  * longer than the 15-bit table, partial or over-long groups); synchronising, diagnostic */
 int dc_huff_decode_redo_count(dc_ctx *ctx, uint64_t *count);
+/* ---- Huffman batch v1: many small buffers, one table each, one call --------------
+ * The reference's own design is blocks of <= 65000 bytes with a table each
+ * (n_ary_huffman.c:1210-1255, :1866-1883); this is its device-resident form for thousands of
+ * independent buffers. A batch is `count` segments d_in[d_in_off[i] .. d_in_off[i+1]) (d_in_off:
+ * device u64, count + 1 entries; any byte alignment; length 0 legal; at most DC_BATCH_SEG_MAX
+ * bytes each). One n_ary (2..256) and one sync size (a power of two, 16..DC_SYNC_MAX) hold for
+ * the batch. For segment i of length len with byte histogram h:
+ *   lens   d_lens[256 i + s], s < 256 (u8, in digits): the first 256 lengths dc_huff_table(h, 258,
+ *          n_ary) gives; the codes are those of dc_huff_table_lengths on them (256..258 at 0).
+ *   mode   d_mode[i] = 1 (Huffman) when every present byte's packed code is <= 32 bits and
+ *          bits < 8 len; else 0 (stored: the payload is the segment's bytes). len 0 is stored.
+ *   bits   d_bits[i] (u32): the payload bits (mode 1) or 8 len (mode 0).
+ *   payload  ceil(bits / 8) bytes at d_payload + d_pay_off[i], MSB-first: exactly the stream
+ *          dc_huff_pack writes for the segment alone at bit_base 0. d_pay_off (u64, count + 1
+ *          entries): pay_off[0] = 0, pay_off[i + 1] = pay_off[i] + round_up_16(ceil(bits / 8));
+ *          the pad bytes are zero, so d_payload[0 .. pay_off[count]) is deterministic, and
+ *          every segment's payload is 16-B aligned (d_payload must be): with a table from
+ *          dc_huff_table_lengths and group bases summed from its sync entries, a Huffman-mode
+ *          segment also decodes with dc_huff_decode.
+ *   sync   d_sync_len (u16) holds ceil(len / sync_syms) entries per segment from
+ *          d_sync_off[i] (u64, count + 1 entries, the exclusive prefix of the entry counts):
+ *          entry c = the bit length of symbols [c S, min((c + 1) S, len)); 8 bits a symbol in a
+ *          stored segment. No group bases: a segment has at most 4096 chunks, scanned in LDS.
+ * d_status[i] (i32) receives each segment's outcome; a bad segment never stops the others:
+ *   DC_E_ARG       longer than DC_BATCH_SEG_MAX, or offsets that decrease: nothing is written
+ *                  for it (not even lens / mode / bits), and it takes 0 payload bytes and 0 sync
+ *                  entries
+ *   DC_E_CAPACITY  its payload or sync entries would pass payload_cap / sync_cap (decode: its
+ *                  output would pass out_cap): nothing of it is written; nothing is ever written
+ *                  past a cap
+ *   DC_E_STREAM    (decode) the mode byte is neither 0 nor 1, a length exceeds DC_MAX_DIGITS or
+ *                  gives a code over 32 bits, the offsets do not fit bits / the asked length,
+ *                  the chunk lengths do not sum to bits, or a chunk does not decode to exactly
+ *                  its symbols in exactly its bits (an invalid or over-long code, a present
+ *                  byte whose length was lost): nothing of the segment is written
+ * Sizing: dc_huff_batch_payload_bound = total_bytes + 16 count (exact as an upper bound: the
+ * stored fallback); dc_huff_batch_sync_bound = ceil(total_bytes / S) + count u16 entries, no
+ * slack: the batch kernels access every entry as a u16 of its own. Both are pure host
+ * arithmetic (csrc/dc_batch_bound.h). */
+#define DC_BATCH_SEG_MAX 65536u
+typedef struct dc_hbatch {
+    uint64_t count;          /* segments                                                  */
+    int32_t n_ary;
+    uint32_t sync_syms;
+    uint8_t *d_lens;         /* 256 x count                                               */
+    uint8_t *d_mode;         /* count                                                     */
+    uint32_t *d_bits;        /* count                                                     */
+    uint64_t *d_pay_off;     /* count + 1                                                 */
+    uint8_t *d_payload;      /* payload_cap bytes, 16-B aligned                           */
+    uint64_t payload_cap;
+    uint64_t *d_sync_off;    /* count + 1                                                 */
+    uint16_t *d_sync_len;    /* sync_cap entries                                          */
+    uint64_t sync_cap;
+    int32_t *d_status;       /* count: written by the last encode / decode of the batch   */
+} dc_hbatch;
+uint64_t dc_huff_batch_payload_bound(uint64_t total_bytes, uint64_t count);
+uint64_t dc_huff_batch_sync_bound(uint64_t total_bytes, uint64_t count, uint32_t sync_syms);
+/* Encode: fills every array of *batch (batch->count must equal count). Asynchronous, no host
+ * read anywhere, and the same launches for any count and any segment sizes: one plan kernel
+ * (a workgroup per segment on a persistent grid: histogram, lengths, canonical codes, the
+ * compact record), two scans (d_pay_off, d_sync_off) and one pack kernel. count 0 returns DC_OK
+ * without a launch. At most DC_RANGES_MAX segments. */
+int dc_huff_encode_batch(dc_ctx *ctx, const uint8_t *d_in, const uint64_t *d_in_off, uint64_t count,
+                         const dc_hbatch *batch);
+/* Decode: segment i -> d_out[d_out_off[i] .. d_out_off[i + 1]) (device u64, count + 1 entries,
+ * any alignment). The length asked for must be the segment's (the format does not store it).
+ * Asynchronous, one launch. No byte of d_out outside the requested ranges is written, and none
+ * of a segment that fails. dc_huff_decode_batch_scatter: the same with each segment's range
+ * given by its own start and end, d_out[d_out_beg[i] .. d_out_end[i]) (count entries each), so
+ * the outputs may lie anywhere in d_out, with gaps and in any order. */
+int dc_huff_decode_batch(dc_ctx *ctx, const dc_hbatch *batch, uint8_t *d_out, const uint64_t *d_out_off,
+                         uint64_t out_cap);
+int dc_huff_decode_batch_scatter(dc_ctx *ctx, const dc_hbatch *batch, uint8_t *d_out, const uint64_t *d_out_beg,
+                                 const uint64_t *d_out_end, uint64_t out_cap);
+/* 0, or the status of the lowest-numbered failing segment of the last batch call on this
+ * context (synchronising) */
+int dc_huff_batch_status(dc_ctx *ctx);
+
 /* base64url text (6 bits per char, MSB-first) of bits [bit_base, bit_base+bits) */
 int dc_huff_base64url(dc_ctx *ctx, const uint32_t *d_words, uint64_t bit_base, uint64_t bits,
                       char *d_text);
