@@ -6267,6 +6267,7 @@ __global__ __launch_bounds__(256) void k_copy_probe(const uint4 *__restrict__ sr
 
 #include "dc_range_kernels.inc"
 #include "dc_batch_kernels.inc"
+#include "dc_batch_shared_kernels.inc"
 
 #ifdef DC_AB_KERNELS
 #include "dc_ab_kernels.inc"
@@ -7327,6 +7328,83 @@ int dc_huff_decode_batch(dc_ctx *c, const dc_hbatch *b, uint8_t *d_out, const ui
 {
     if (b && b->count && !d_out_off) return DC_E_ARG;
     return dc_huff_decode_batch_scatter(c, b, d_out, d_out_off, d_out_off + 1, out_cap);
+}
+
+// the shared-table mode (dc_batch_shared_kernels.inc): hbatch_args without d_lens, with a table
+static int hbatch_shared_args(dc_ctx *c, const dc_hbatch *b, const dc_dtable *d_table)
+{
+    if (!c || !b || !d_table) return DC_E_ARG;
+    if (b->n_ary < 2 || b->n_ary > 256 || !sync_ok(b->sync_syms)) return DC_E_ARG;
+    if (b->count == 0) return DC_OK;
+    if (!b->d_mode || !b->d_bits || !b->d_pay_off || !b->d_sync_off || !b->d_status) return DC_E_ARG;
+    if ((!b->d_payload && b->payload_cap) || (!b->d_sync_len && b->sync_cap)) return DC_E_ARG;
+    if (((uintptr_t)b->d_payload) & 15) return DC_E_ARG;
+    return DC_OK;
+}
+
+int dc_huff_encode_batch_shared(dc_ctx *c, const uint8_t *d_in, const uint64_t *d_in_off, uint64_t count,
+                                const dc_dtable *d_table, const dc_hbatch *b)
+{
+    if (const int r = hbatch_shared_args(c, b, d_table)) return r;
+    if (b->count != count) return DC_E_ARG;
+    if (count == 0) return DC_OK;
+    if (!d_in_off || count > DC_RANGES_MAX) return DC_E_ARG;
+    if (ensure((void **)&c->d_hb, &c->hb_cap, (2 * count + 2) * sizeof(uint64_t))) return DC_E_HIP;
+    unsigned long long *const first = reinterpret_cast<unsigned long long *>(c->d_hb);
+    uint64_t *const psize = c->d_hb + 2, *const nch = c->d_hb + 2 + count;
+    HIPCHK(hipMemsetAsync(first, 0xFF, sizeof(uint64_t), c->stream));
+    // persistent grids: the plan's LDS is 288 B (4 workgroups a CU), the pack's stage allows 2
+    const uint64_t cap4 = c->opt_batch_grid ? c->opt_batch_grid : 1024, cap2 = c->opt_batch_grid ? c->opt_batch_grid : 512;
+    const uint64_t g4 = count < cap4 ? count : cap4, g2 = count < cap2 ? count : cap2;
+    LAUNCH(c, "hbs_plan", k_hbs_plan, g4, HB_THREADS, d_in, d_in_off, count, (int)b->n_ary, b->sync_syms, d_table, b->d_mode,
+           b->d_bits, psize, nch, b->d_status, first);
+    LAUNCH(c, "hb_scan_pay", k_scan_u64, 1, 1024, (const uint64_t *)psize, count, b->d_pay_off);
+    LAUNCH(c, "hb_scan_sync", k_scan_u64, 1, 1024, (const uint64_t *)nch, count, b->d_sync_off);
+    LAUNCH(c, "hbs_pack", k_hbs_pack, g2, HB_THREADS, d_in, d_in_off, count, b->sync_syms, d_table, (const uint8_t *)b->d_mode,
+           (const uint64_t *)b->d_pay_off, b->d_payload, b->payload_cap, (const uint64_t *)b->d_sync_off, b->d_sync_len,
+           b->sync_cap, b->d_status, first);
+    return DC_OK;
+}
+
+int dc_huff_decode_batch_shared_scatter(dc_ctx *c, const dc_hbatch *b, const dc_dtable *d_table, uint8_t *d_out,
+                                        const uint64_t *d_out_beg, const uint64_t *d_out_end, uint64_t out_cap)
+{
+    if (const int r = hbatch_shared_args(c, b, d_table)) return r;
+    const uint64_t count = b->count;
+    if (count == 0) return DC_OK;
+    if (!d_out_beg || !d_out_end || (!d_out && out_cap) || count > DC_RANGES_MAX) return DC_E_ARG;
+    if (ensure((void **)&c->d_hb, &c->hb_cap, (2 * count + 2) * sizeof(uint64_t))) return DC_E_HIP;
+    unsigned long long *const first = reinterpret_cast<unsigned long long *>(c->d_hb);
+    HIPCHK(hipMemsetAsync(first, 0xFF, sizeof(uint64_t), c->stream));
+    const uint64_t cap2 = c->opt_batch_grid ? c->opt_batch_grid : 512;
+    const uint64_t groups = (count + 3) / 4;   // a workgroup takes four segments at a time
+    const uint64_t g2 = groups < cap2 ? groups : cap2;
+    LAUNCH(c, "hbs_decode", k_hbs_decode, g2, HB_THREADS, count, (int)b->n_ary, hbatch_w(b->n_ary), b->sync_syms, d_table,
+           (const uint8_t *)b->d_mode, (const uint32_t *)b->d_bits, (const uint64_t *)b->d_pay_off,
+           (const uint8_t *)b->d_payload, b->payload_cap, (const uint64_t *)b->d_sync_off, (const uint16_t *)b->d_sync_len,
+           b->sync_cap, d_out, d_out_beg, d_out_end, out_cap, b->d_status, first);
+    return DC_OK;
+}
+
+int dc_huff_decode_batch_shared(dc_ctx *c, const dc_hbatch *b, const dc_dtable *d_table, uint8_t *d_out,
+                                const uint64_t *d_out_off, uint64_t out_cap)
+{
+    if (b && b->count && !d_out_off) return DC_E_ARG;
+    return dc_huff_decode_batch_shared_scatter(c, b, d_table, d_out, d_out_off, d_out_off + 1, out_cap);
+}
+
+int dc_huff_table_get_lengths(dc_ctx *c, const dc_dtable *d_table, int32_t *h_lengths, int max_entries, int *h_count)
+{
+    if (!c || !d_table || !h_count || max_entries < 0 || (max_entries && !h_lengths)) return DC_E_ARG;
+    int32_t M = -1;
+    HIPCHK(hipMemcpyAsync(&M, &d_table->max_symbol_value, sizeof(M), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (M < 0 || M >= DC_MAX_SYMS) return DC_E_ARG;   // not a table the table kernels wrote
+    *h_count = M + 1;
+    if (max_entries < M + 1) return DC_E_CAPACITY;
+    HIPCHK(hipMemcpyAsync(h_lengths, d_table->lengths, (size_t)(M + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return DC_OK;
 }
 
 int dc_huff_batch_status(dc_ctx *c)

@@ -546,14 +546,18 @@ class Codec:
         return v
 
     def encode_batch(self, x, offsets, n_ary: int = 2, sync_syms: int = 64, payload=None, sync_len=None,
-                     payload_cap=None, sync_cap=None):
+                     payload_cap=None, sync_cap=None, table=None):
         """dc_huff_encode_batch: segment i = x[offsets[i]:offsets[i+1]] (device uint8 x, int64
         offsets of count + 1 entries, any alignment, each segment <= 65536 bytes) coded under a
         table of its own, or stored when that is not smaller. Asynchronous, no host read; the
         launches do not depend on count. Returns a dict of device tensors: lens (count x 256
         u8), mode, bits, pay_off, payload, sync_off, sync_len, status (per segment; see
         batch_status()). payload / sync_len: optional preallocated buffers (else sized by
-        batch_bounds); payload_cap / sync_cap: smaller caps to hand to the kernels."""
+        batch_bounds); payload_cap / sync_cap: smaller caps to hand to the kernels.
+        table: a device table (table(), table_lengths(), batch_table()) of the same n_ary that
+        codes EVERY segment (dc_huff_encode_batch_shared): no table work per segment and no
+        lens record; a segment holding a byte without a code under it is stored. The result
+        then carries "table": table and "lens": None."""
         if x.dtype != torch.uint8 or not x.is_contiguous():
             raise ValueError("encode_batch input: contiguous uint8")
         offsets = self._i64(offsets, range(1, 1 << 62), "encode_batch offsets")
@@ -562,18 +566,25 @@ class Codec:
         payload = payload if payload is not None else self._t(max(pb, 16))
         sync_len = sync_len if sync_len is not None else self._t(max(sb, 1), torch.int16)
         enc = {"count": count, "n_ary": n_ary, "S": sync_syms, "offsets": offsets, "total": x.numel(),
-               "lens": self._t(max(count, 1) * 256).view(max(count, 1), 256)[:count], "mode": self._t(max(count, 1))[:count],
+               "lens": self._t(max(count, 1) * 256).view(max(count, 1), 256)[:count] if table is None else None,
+               "mode": self._t(max(count, 1))[:count],
                "bits": self._t(max(count, 1), torch.int32)[:count], "pay_off": self._t(count + 1, torch.int64),
                "payload": payload, "sync_off": self._t(count + 1, torch.int64), "sync_len": sync_len,
                "status": self._t(max(count, 1), torch.int32)[:count]}
         b = self._hbatch(enc, payload_cap, sync_cap)
         enc["payload_cap"], enc["sync_cap"] = int(b.payload_cap), int(b.sync_cap)
+        if table is not None:
+            enc["table"] = table
+            check("dc_huff_encode_batch_shared",
+                  self.L.dc_huff_encode_batch_shared(self.ctx, _ptr(x), _ptr(offsets), count, _ptr(table), C.byref(b)))
+            return enc
         check("dc_huff_encode_batch", self.L.dc_huff_encode_batch(self.ctx, _ptr(x), _ptr(offsets), count, C.byref(b)))
         return enc
 
     def encode_blocks(self, x, block: int = 65536, **kw):
         """encode_batch of x cut into independent blocks of `block` bytes (the last shorter),
-        a table each: the reference's own block design (n_ary_huffman.c:1210-1255)."""
+        a table each: the reference's own block design (n_ary_huffman.c:1210-1255); with
+        table=..., all under that one table."""
         if not 0 < block <= self.SEG_MAX:
             raise ValueError("encode_blocks: 0 < block <= 65536")
         n = x.numel()
@@ -586,8 +597,10 @@ class Codec:
         entries give each segment's start alone (its length is the encoded segment's), so the
         outputs may lie anywhere in out (dc_huff_decode_batch_scatter). Default: the segments
         back to back from 0. Asynchronous; returns (out, out_off). Per-segment outcome in
-        enc["status"], the first failure by batch_status()."""
+        enc["status"], the first failure by batch_status(). A batch encoded under a shared
+        table (enc["table"]) is decoded under it (dc_huff_decode_batch_shared)."""
         count = enc["count"]
+        table = enc.get("table")
         if out_off is None:
             out_off = enc["offsets"] - enc["offsets"][:1]
         out_off = self._i64(out_off, (count, count + 1), "decode_batch out_off")
@@ -597,14 +610,34 @@ class Codec:
                 raise ValueError("decode_batch: segment starts alone need an output buffer")
         buf = self._u8_out(out, "decode_batch")
         b = self._hbatch(enc, enc["payload_cap"], enc["sync_cap"])
+        tab = () if table is None else (_ptr(table),)
         if out_off.numel() == count + 1:
-            check("dc_huff_decode_batch", self.L.dc_huff_decode_batch(self.ctx, C.byref(b), _ptr(buf), _ptr(out_off),
-                                                                      buf.numel()))
+            fn = "dc_huff_decode_batch" if table is None else "dc_huff_decode_batch_shared"
+            check(fn, getattr(self.L, fn)(self.ctx, C.byref(b), *tab, _ptr(buf), _ptr(out_off), buf.numel()))
         else:
             end = out_off + (enc["offsets"][1:] - enc["offsets"][:-1])
-            check("dc_huff_decode_batch_scatter", self.L.dc_huff_decode_batch_scatter(
-                self.ctx, C.byref(b), _ptr(buf), _ptr(out_off), _ptr(end), buf.numel()))
+            fn = "dc_huff_decode_batch_scatter" if table is None else "dc_huff_decode_batch_shared_scatter"
+            check(fn, getattr(self.L, fn)(self.ctx, C.byref(b), *tab, _ptr(buf), _ptr(out_off), _ptr(end), buf.numel()))
         return out, out_off
+
+    def batch_table(self, x, n_ary: int = 2):
+        """The table of the whole input x (device uint8): hist plus table, for
+        encode_batch(..., table=...). dc_huff_hist wants a 16-B aligned input: a misaligned x is
+        cloned."""
+        if x.dtype != torch.uint8 or not x.is_contiguous():
+            raise ValueError("batch_table input: contiguous uint8")
+        if x.data_ptr() & 15:
+            x = x.clone()
+        return self.table(self.hist(x), n_ary)
+
+    def table_get_lengths(self, tab):
+        """dc_huff_table_get_lengths: the table's lengths in digits, entries 0 ..
+        max_symbol_value, as a numpy int32 array (what table_lengths takes back). Synchronising."""
+        buf = np.zeros(1024, np.int32)   # DC_MAX_SYMS
+        n = C.c_int(0)
+        check("dc_huff_table_get_lengths", self.L.dc_huff_table_get_lengths(
+            self.ctx, _ptr(tab), buf.ctypes.data_as(C.POINTER(C.c_int32)), buf.size, C.byref(n)))
+        return buf[: n.value].copy()
 
     def batch_status(self) -> int:
         """0, or the status of the lowest-numbered failing segment of the last encode_batch /

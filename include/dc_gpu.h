@@ -137,7 +137,8 @@ enum {
                                      4096-element tile with a workgroup (k_fsm_write) instead of a
                                      wave (k_nyb_enc_wtile / k_nyb_dec_wtile) */
     DC_OPT_BATCH_GRID = 10        /* batch codec: workgroups of its persistent kernels, 0 = what a
-                                     256-CU device holds at once (768 plan, 512 pack / decode) */
+                                     256-CU device holds at once (768 plan, 512 pack / decode; the
+                                     shared-table mode: 1024 plan, 512 pack / decode) */
 };
 int dc_ctx_set_option(dc_ctx *ctx, int option, int64_t value);
 const char *dc_version(void);
@@ -405,6 +406,50 @@ int dc_huff_decode_batch_scatter(dc_ctx *ctx, const dc_hbatch *batch, uint8_t *d
 /* 0, or the status of the lowest-numbered failing segment of the last batch call on this
  * context (synchronising) */
 int dc_huff_batch_status(dc_ctx *ctx);
+/* ---- Huffman batch v1, shared table: every segment under ONE dc_dtable ------------------------
+ * A mode of the same dc_hbatch for thousands of small, similar buffers (pages, records, rows):
+ * the table is built once (from the whole batch, or from a training sample), stored once, and
+ * every segment still decodes alone. Everything is as in batch v1 except that there is no
+ * per-segment lens record (batch->d_lens is neither read nor written and may be NULL) and
+ * *d_table holds for the whole batch. With nb[s] = d_table->nbits[s], code[s] = d_table->code[s],
+ * for segment i of length len:
+ *   mode   1 when len > 0, every byte of the segment has nb != 0, and bits = sum nb[byte] < 8 len;
+ *          else 0 (stored, bits = 8 len). A byte without a code under the table (also one whose
+ *          code passes 32 bits: the table kernels leave its nbits 0) makes that segment stored; it
+ *          is never an error, so a trained table is safe on any input.
+ *   payload, pay_off, sync_len, sync_off, the zero pads, the 16-B alignment, both bound functions,
+ *          the statuses and "nothing is written for a failed segment or past a cap": batch v1's.
+ *          A mode-1 payload is bit for bit what dc_huff_pack writes for the segment alone at bit 0
+ *          under d_table, so it also decodes with dc_huff_decode under that table.
+ * batch->n_ary must equal the table's n_ary, and the table's status must be DC_OK or
+ * DC_E_CODE_TOO_LONG (such a table is usable: its over-long codes are "no code"). The kernels read
+ * both on the device (no host read); otherwise every segment gets DC_E_ARG and nothing is written.
+ * The table is const: the kernels read code / nbits (decode also first / count / start / syms /
+ * min_len / max_len), never dec_ready or dlut*, and write nothing into it, so one table serves
+ * many contexts and streams at once, and a table rebuilt elsewhere by dc_huff_table_lengths from
+ * the same lengths (dc_huff_table_get_lengths) decodes the batch. What to store: the lengths once,
+ * then mode, bits, the payload and the u16 index per segment.
+ * Decoding under a different table is reported as DC_E_STREAM whenever a chunk then fails to
+ * decode to exactly its symbols in exactly its bits; as in batch v1 there is no checksum, so a
+ * wrong table that happens to satisfy every chunk is not detected. A window that decodes to a
+ * symbol >= 256 (the table's canonical arrays hold up to DC_MAX_SYMS symbols) is a corrupt stream,
+ * never a byte written.
+ * Host argument rules are batch v1's without the d_lens test, and d_table must not be NULL. All
+ * three calls are asynchronous and make no host read; count 0 returns DC_OK without a launch;
+ * dc_huff_batch_status answers for them; DC_OPT_BATCH_GRID sizes their grids. Encode: one plan
+ * kernel (no histogram, no table work), the two scans, one pack kernel. Decode: one launch, the
+ * first-level table and the long-code arrays built once per workgroup, not per segment. */
+int dc_huff_encode_batch_shared(dc_ctx *ctx, const uint8_t *d_in, const uint64_t *d_in_off, uint64_t count,
+                                const dc_dtable *d_table, const dc_hbatch *batch);
+int dc_huff_decode_batch_shared(dc_ctx *ctx, const dc_hbatch *batch, const dc_dtable *d_table,
+                                uint8_t *d_out, const uint64_t *d_out_off, uint64_t out_cap);
+int dc_huff_decode_batch_shared_scatter(dc_ctx *ctx, const dc_hbatch *batch, const dc_dtable *d_table,
+                                        uint8_t *d_out, const uint64_t *d_out_beg, const uint64_t *d_out_end,
+                                        uint64_t out_cap);
+/* the table's lengths in digits, entries 0 .. max_symbol_value (what dc_huff_table_lengths takes
+ * back): all a shared batch needs stored beside its arrays. *h_count receives max_symbol_value + 1;
+ * DC_E_CAPACITY (nothing copied) when max_entries is smaller. Synchronising. */
+int dc_huff_table_get_lengths(dc_ctx *ctx, const dc_dtable *d_table, int32_t *h_lengths, int max_entries, int *h_count);
 
 /* base64url text (6 bits per char, MSB-first) of bits [bit_base, bit_base+bits) */
 int dc_huff_base64url(dc_ctx *ctx, const uint32_t *d_words, uint64_t bit_base, uint64_t bits,

@@ -7,8 +7,13 @@ of bench.py (synth.device_text, seed 0xC2, n = 2, S = 64), one process:
   loop    4096 x 4 KiB: the batch call against the loop of Codec.encode / decode_into over the
           same segments (all a caller could do before), wall clock around calls that end
           synchronised, the two sides alternating; asserts that the batch call is faster
+  shared  the same blocks under ONE table of the whole text (Codec.batch_table, encode_blocks(...,
+          table=)): encode and decode ms, the stage split, and the stored size (payload + u16
+          index + 5 B per segment + the table's lengths once) beside the own-table size; then at
+          4 KiB the own-table call against the shared call, alternating in this process; asserts
+          that the shared encode and decode are each faster and that the shared form is smaller
 Every result is checked against the input before it is timed. One JSON line per result.
-    timeout 900 python tools/batch_bench.py [--size BYTES] [--steps K] [--rounds R] [--only blocks,loop]
+    timeout 900 python tools/batch_bench.py [--size BYTES] [--steps K] [--rounds R] [--only blocks,loop,shared]
 """
 import argparse
 import json
@@ -27,7 +32,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--size", type=int, default=1 << 30)
 ap.add_argument("--steps", type=int, default=5)
 ap.add_argument("--rounds", type=int, default=5)
-ap.add_argument("--only", default="blocks,loop")
+ap.add_argument("--only", default="blocks,loop,shared")
 a = ap.parse_args()
 assert torch.cuda.is_available(), "batch_bench needs a GPU"
 dev = "cuda:0"
@@ -148,3 +153,61 @@ if "loop" in a.only:
          decode_speedup=round(med["loop_decode"] / med["batch_decode"], 1))
     assert med["batch_encode"] < med["loop_encode"] and med["batch_decode"] < med["loop_decode"], \
         "the batch call is not faster than the loop of single-stream calls"
+
+if "shared" in a.only:
+    tab = c.batch_table(x, n_ary=2)
+    lengths = c.table_get_lengths(tab)
+    assert lengths.max() <= 255   # a byte each in a container
+    out = torch.empty(n, dtype=torch.uint8, device=dev)
+    for block in (65536, 4096):
+        count = (n + block - 1) // block
+        pb, sb = c.batch_bounds(n, count, S)
+        bufs = {k: (torch.empty(pb, dtype=torch.uint8, device=dev), torch.empty(sb, dtype=torch.int16, device=dev))
+                for k in ("own", "shared")}
+
+        def encode(kind):
+            return c.encode_blocks(x, block=block, n_ary=2, sync_syms=S, payload=bufs[kind][0], sync_len=bufs[kind][1],
+                                   **({"table": tab} if kind == "shared" else {}))
+
+        encs, size = {}, {}
+        for kind in ("own", "shared"):
+            enc = encs[kind] = encode(kind)
+            assert c.batch_status() == 0
+            out.zero_()
+            c.decode_batch(enc, out=out, out_off=enc["offsets"])
+            assert c.batch_status() == 0 and torch.equal(out, x), kind + ": batch round trip differs from the input"
+            pay, idx = int(enc["pay_off"][-1]), int(enc["sync_off"][-1])
+            # per segment: mode (1), bits (4), the payload, the u16 index; a lens record (256) each, or the lengths once
+            size[kind] = pay + 2 * idx + count * 5 + (count * 256 if kind == "own" else lengths.size)
+            emit(what="shared_size", table=kind, block=block, count=count, payload_bytes=pay, sync_entries=idx,
+                 stored_bytes=size[kind], huffman_segments=int(enc["mode"].sum()), payload_bits_per_byte=round(8 * pay / n, 4))
+        emit(what="shared_vs_own_size", block=block, own=size["own"], shared=size["shared"],
+             shared_smaller_pct=round(100 * (1 - size["shared"] / size["own"]), 2))
+        off = encs["shared"]["offsets"]
+        e_ms, e_mm = median_ms(lambda: encode("shared"), a.steps, a.rounds)
+        d_ms, d_mm = median_ms(lambda: c.decode_batch(encs["shared"], out=out, out_off=off), a.steps, a.rounds)
+        emit(what="shared_time", block=block, count=count, encode_ms=round(e_ms, 3), encode_GBps=round(n / e_ms / 1e6, 1),
+             decode_ms=round(d_ms, 3), decode_GBps=round(n / d_ms / 1e6, 1), encode_min_max_ms=e_mm, decode_min_max_ms=d_mm)
+        c.timing(True)
+        encode("shared")
+        c.decode_batch(encs["shared"], out=out, out_off=off)
+        emit(what="shared_stages", block=block, ms={k: round(v, 4) for k, v in c.timings()})
+        c.timing(False)
+        if block == 4096:   # the yardstick: the own-table call of this build, the two sides alternating
+            fns = {"own_encode": lambda: encode("own"), "shared_encode": lambda: encode("shared"),
+                   "own_decode": lambda: c.decode_batch(encs["own"], out=out, out_off=off),
+                   "shared_decode": lambda: c.decode_batch(encs["shared"], out=out, out_off=off)}
+            t = {k: [] for k in fns}
+            for _ in range(a.rounds):
+                for k, fn in fns.items():
+                    t[k].append(ev_ms(fn, a.steps))
+            med = {k: round(statistics.median(v), 3) for k, v in t.items()}
+            emit(what="shared_vs_own_time", block=block, count=count, ms=med,
+                 min_max_ms={k: (round(min(v), 3), round(max(v), 3)) for k, v in t.items()},
+                 encode_speedup=round(med["own_encode"] / med["shared_encode"], 2),
+                 decode_speedup=round(med["own_decode"] / med["shared_decode"], 2))
+            assert med["shared_encode"] < med["own_encode"], "the shared-table encode is not faster than the own-table encode"
+            assert med["shared_decode"] < med["own_decode"], "the shared-table decode is not faster than the own-table decode"
+            assert size["shared"] < size["own"], "the shared-table form is not smaller than the own-table form"
+        del encs, bufs
+    del out
