@@ -19,6 +19,11 @@
 //                 and a byte tail
 // A segment's status goes to status[i]; the lowest failing (index, status) of the call is kept
 // in *first (atomicMin) for dc_huff_batch_status.
+// What a segment takes once its table is in LDS is here once, for this mode and for the shared-
+// table mode (dc_batch_shared_kernels.inc): hb_pack_seg (the whole of a pack), hb_decode_check and
+// hb_decode_body (the validation of a segment, and its chunk loop, commit and phased write) and
+// hb_decode_slow. The kernels differ in where the table comes from: k_hb_pack and k_hb_decode
+// build it per segment from lens (hb_canonical), the shared kernels copy it once per workgroup.
 
 #define HB_THREADS 256
 #define HB_UNIT 16                                   /* symbols per pack work unit (divides S)  */
@@ -174,14 +179,19 @@ static __device__ void hb_canonical(HbCode &C, const uint8_t *__restrict__ lens,
 }
 
 // ---- pack -------------------------------------------------------------------------------------
-struct HbPackLds {
+// the LDS a segment is packed in, beside the code table of the kernel that packs it
+struct HbPackWork {
     __attribute__((aligned(16))) uint32_t stage[DC_BATCH_SEG_MAX / 4];   // the payload, word bit 31 first
-    HbCode C;
     uint16_t ulen[HB_UNITS_MAX];   // bits per 16-symbol unit
     uint32_t tbase[HB_THREADS];    // bit offset of unit 16 t
     uint32_t scan[4];
 };
 static_assert(HB_UNITS_MAX == 16 * HB_THREADS, "the unit scan gives every thread 16 units");
+
+struct HbPackLds {
+    HbPackWork P;
+    HbCode C;
+};
 
 // bytes p[at .. at + 16) of a segment of len bytes (at < len) as 4 little-endian dwords, by
 // aligned dword loads: only dwords that hold a byte of the segment are read; the bytes at and
@@ -198,6 +208,107 @@ static __device__ __forceinline__ void hb_load16(const uint8_t *__restrict__ p, 
     for (int j = 0; j < 4; ++j) q[j] = __builtin_amdgcn_alignbyte(d[j + 1], d[j], a);
 }
 
+// segment i (status DC_OK by its plan) by the whole workgroup, under the byte codes code[] / nb[]
+// (nb 0: no code) that the caller has ready in LDS; a stored segment reads neither. Every barrier
+// is reached by the whole workgroup: the tests before one are uniform.
+static __device__ __forceinline__ void hb_pack_seg(
+    HbPackWork &P, const uint32_t (&code)[256], const uint32_t (&nb)[256], uint64_t i, const uint8_t *__restrict__ in,
+    const uint64_t *__restrict__ in_off, uint32_t S, const uint8_t *__restrict__ mode, const uint64_t *__restrict__ pay_off,
+    uint8_t *__restrict__ payload, uint64_t payload_cap, const uint64_t *__restrict__ sync_off, uint16_t *__restrict__ sync_len,
+    uint64_t sync_cap, int32_t *__restrict__ status, unsigned long long *__restrict__ first)
+{
+    const int t = threadIdx.x;
+    const uint32_t slog = (uint32_t)__builtin_ctz(S);
+    const uint64_t a = in_off[i];
+    const uint32_t len = (uint32_t)(in_off[i + 1] - a);
+    const uint64_t po = pay_off[i], pe = pay_off[i + 1], so = sync_off[i], se = sync_off[i + 1];
+    if (pe > payload_cap || se > sync_cap) {
+        if (t == 0) hb_fail(status, first, i, DC_E_CAPACITY);
+        return;
+    }
+    if (len == 0) return;
+    const uint32_t psz = (uint32_t)(pe - po), nch = (uint32_t)(se - so);
+    const uint8_t *p = in + a;
+    uint4 *const dst = reinterpret_cast<uint4 *>(payload + po);   // (po and payload 16-B aligned)
+    if (mode[i] == 0) {   // stored: the bytes, zero-padded to 16
+        for (uint32_t v = t; v < psz / 16; v += HB_THREADS) {
+            uint32_t q[4];
+            hb_load16(p, 16 * v, len, q);
+            const uint32_t left = len - 16 * v;   // (> 0: psz = pad16(len))
+#pragma unroll
+            for (uint32_t j = 0; j < 4; ++j) {
+                if (left <= 4 * j) q[j] = 0;
+                else if (left < 4 * j + 4) q[j] &= (1u << (8 * (left - 4 * j))) - 1u;
+            }
+            dst[v] = make_uint4(q[0], q[1], q[2], q[3]);
+        }
+        for (uint32_t c = t; c < nch; c += HB_THREADS) {
+            const uint32_t left = len - (c << slog);
+            sync_len[so + c] = (uint16_t)(8u * (left < S ? left : S));
+        }
+        return;
+    }
+    for (uint32_t k = t; k < psz / 4; k += HB_THREADS) P.stage[k] = 0;
+    // unit u (16 symbols) by thread u % 256: its bit length, then the scan (thread t sums
+    // units 16 t .. 16 t + 15), then its codes OR-ed into the stage at its bit offset
+    const uint32_t units = (len + HB_UNIT - 1) / HB_UNIT;
+    for (uint32_t u = t; u < units; u += HB_THREADS) {
+        uint32_t q[4];
+        hb_load16(p, u * HB_UNIT, len, q);
+        const uint32_t cntu = min((uint32_t)HB_UNIT, len - u * HB_UNIT);
+        uint32_t ub = 0;
+#pragma unroll
+        for (uint32_t k = 0; k < HB_UNIT; ++k)
+            if (k < cntu) ub += nb[(q[k >> 2] >> (8 * (k & 3))) & 255u];
+        P.ulen[u] = (uint16_t)ub;   // <= 16 * 32
+    }
+    __syncthreads();
+    uint32_t tsum = 0;
+    for (uint32_t u = 16 * (uint32_t)t; u < min(16 * (uint32_t)t + 16, units); ++u) tsum += P.ulen[u];
+    uint32_t total;
+    P.tbase[t] = wg_scan_excl_u32(tsum, P.scan, &total);
+    __syncthreads();
+    {   // the sync index: chunk c = units [c r, (c + 1) r), r = S / 16
+        const uint32_t r = S / HB_UNIT;
+        for (uint32_t c = t; c < nch; c += HB_THREADS) {
+            const uint32_t e = min((c + 1) * r, units);
+            uint32_t cb = 0;
+            for (uint32_t u = c * r; u < e; ++u) cb += P.ulen[u];
+            sync_len[so + c] = (uint16_t)cb;   // <= 1024 * 32
+        }
+    }
+    for (uint32_t u = t; u < units; u += HB_THREADS) {
+        uint32_t pos = P.tbase[u >> 4];
+        for (uint32_t k = u & ~15u; k < u; ++k) pos += P.ulen[k];
+        uint32_t q[4];
+        hb_load16(p, u * HB_UNIT, len, q);
+        const uint32_t cntu = min((uint32_t)HB_UNIT, len - u * HB_UNIT);
+        // a 64-bit accumulator, whole words OR-ed into the stage (neighbours share words)
+        uint32_t wi = pos >> 5, nacc = pos & 31u;
+        uint64_t acc = 0;
+#pragma unroll
+        for (uint32_t k = 0; k < HB_UNIT; ++k) {
+            if (k < cntu) {
+                const uint32_t b = (q[k >> 2] >> (8 * (k & 3))) & 255u, n = nb[b];
+                if (n) acc |= (uint64_t)code[b] << (64u - nacc - n);
+                nacc += n;
+                if (nacc >= 32u) {
+                    if (wi < DC_BATCH_SEG_MAX / 4) atomicOr(&P.stage[wi], (uint32_t)(acc >> 32));
+                    ++wi;
+                    acc <<= 32;
+                    nacc -= 32u;
+                }
+            }
+        }
+        if (nacc && wi < DC_BATCH_SEG_MAX / 4) atomicOr(&P.stage[wi], (uint32_t)(acc >> 32));
+    }
+    __syncthreads();
+    for (uint32_t v = t; v < psz / 16; v += HB_THREADS) {
+        const uint4 q = reinterpret_cast<const uint4 *>(P.stage)[v];
+        dst[v] = make_uint4(bswap32(q.x), bswap32(q.y), bswap32(q.z), bswap32(q.w));
+    }
+}
+
 __global__ __launch_bounds__(HB_THREADS) void k_hb_pack(const uint8_t *__restrict__ in, const uint64_t *__restrict__ in_off,
                                                         uint64_t count, int nary, int w, uint32_t S,
                                                         const uint8_t *__restrict__ lens, const uint8_t *__restrict__ mode,
@@ -207,124 +318,59 @@ __global__ __launch_bounds__(HB_THREADS) void k_hb_pack(const uint8_t *__restric
                                                         int32_t *__restrict__ status, unsigned long long *__restrict__ first)
 {
     __shared__ HbPackLds L;
-    const int t = threadIdx.x;
-    const uint32_t slog = (uint32_t)__builtin_ctz(S);
     for (uint64_t i = blockIdx.x; i < count; i += gridDim.x) {
         __syncthreads();   // the LDS of the segment before
         if (status[i] != DC_OK) continue;   // (DC_E_ARG by the plan; uniform)
-        const uint64_t a = in_off[i];
-        const uint32_t len = (uint32_t)(in_off[i + 1] - a);
-        const uint64_t po = pay_off[i], pe = pay_off[i + 1], so = sync_off[i], se = sync_off[i + 1];
-        if (pe > payload_cap || se > sync_cap) {
-            if (t == 0) hb_fail(status, first, i, DC_E_CAPACITY);
-            continue;
-        }
-        if (len == 0) continue;
-        const uint32_t psz = (uint32_t)(pe - po), nch = (uint32_t)(se - so);
-        const uint8_t *p = in + a;
-        uint4 *const dst = reinterpret_cast<uint4 *>(payload + po);   // (po and payload 16-B aligned)
-        if (mode[i] == 0) {   // stored: the bytes, zero-padded to 16
-            for (uint32_t v = t; v < psz / 16; v += HB_THREADS) {
-                uint32_t q[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    uint32_t x = 0;
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        const uint32_t at = 16 * v + 4 * j + k;
-                        if (at < len) x |= (uint32_t)p[at] << (8 * k);
-                    }
-                    q[j] = x;
-                }
-                dst[v] = make_uint4(q[0], q[1], q[2], q[3]);
-            }
-            for (uint32_t c = t; c < nch; c += HB_THREADS) {
-                const uint32_t left = len - (c << slog);
-                sync_len[so + c] = (uint16_t)(8u * (left < S ? left : S));
-            }
-            continue;
-        }
-        hb_canonical(L.C, lens + i * 256, nary, w);
-        for (uint32_t k = t; k < psz / 4; k += HB_THREADS) L.stage[k] = 0;
-        // unit u (16 symbols) by thread u % 256: its bit length, then the scan (thread t sums
-        // units 16 t .. 16 t + 15), then its codes OR-ed into the stage at its bit offset
-        const uint32_t units = (len + HB_UNIT - 1) / HB_UNIT;
-        for (uint32_t u = t; u < units; u += HB_THREADS) {
-            uint32_t q[4];
-            hb_load16(p, u * HB_UNIT, len, q);
-            const uint32_t cntu = min((uint32_t)HB_UNIT, len - u * HB_UNIT);
-            uint32_t ub = 0;
-#pragma unroll
-            for (uint32_t k = 0; k < HB_UNIT; ++k)
-                if (k < cntu) ub += L.C.nb[(q[k >> 2] >> (8 * (k & 3))) & 255u];
-            L.ulen[u] = (uint16_t)ub;   // <= 16 * 32
-        }
-        __syncthreads();
-        uint32_t tsum = 0;
-        for (uint32_t u = 16 * (uint32_t)t; u < min(16 * (uint32_t)t + 16, units); ++u) tsum += L.ulen[u];
-        uint32_t total;
-        L.tbase[t] = wg_scan_excl_u32(tsum, L.scan, &total);
-        __syncthreads();
-        {   // the sync index: chunk c = units [c r, (c + 1) r), r = S / 16
-            const uint32_t r = S / HB_UNIT;
-            for (uint32_t c = t; c < nch; c += HB_THREADS) {
-                const uint32_t e = min((c + 1) * r, units);
-                uint32_t cb = 0;
-                for (uint32_t u = c * r; u < e; ++u) cb += L.ulen[u];
-                sync_len[so + c] = (uint16_t)cb;   // <= 1024 * 32
-            }
-        }
-        for (uint32_t u = t; u < units; u += HB_THREADS) {
-            uint32_t pos = L.tbase[u >> 4];
-            for (uint32_t k = u & ~15u; k < u; ++k) pos += L.ulen[k];
-            uint32_t q[4];
-            hb_load16(p, u * HB_UNIT, len, q);
-            const uint32_t cntu = min((uint32_t)HB_UNIT, len - u * HB_UNIT);
-            // a 64-bit accumulator, whole words OR-ed into the stage (neighbours share words)
-            uint32_t wi = pos >> 5, nacc = pos & 31u;
-            uint64_t acc = 0;
-#pragma unroll
-            for (uint32_t k = 0; k < HB_UNIT; ++k) {
-                if (k < cntu) {
-                    const uint32_t b = (q[k >> 2] >> (8 * (k & 3))) & 255u, nb = L.C.nb[b];
-                    if (nb) acc |= (uint64_t)L.C.code[b] << (64u - nacc - nb);
-                    nacc += nb;
-                    if (nacc >= 32u) {
-                        if (wi < DC_BATCH_SEG_MAX / 4) atomicOr(&L.stage[wi], (uint32_t)(acc >> 32));
-                        ++wi;
-                        acc <<= 32;
-                        nacc -= 32u;
-                    }
-                }
-            }
-            if (nacc && wi < DC_BATCH_SEG_MAX / 4) atomicOr(&L.stage[wi], (uint32_t)(acc >> 32));
-        }
-        __syncthreads();
-        for (uint32_t v = t; v < psz / 16; v += HB_THREADS) {
-            const uint4 q = reinterpret_cast<const uint4 *>(L.stage)[v];
-            dst[v] = make_uint4(bswap32(q.x), bswap32(q.y), bswap32(q.z), bswap32(q.w));
-        }
+        if (mode[i] != 0) hb_canonical(L.C, lens + i * 256, nary, w);   // (uniform; a stored segment has no use for codes)
+        hb_pack_seg(L.P, L.C.code, L.C.nb, i, in, in_off, S, mode, pay_off, payload, payload_cap, sync_off, sync_len, sync_cap,
+                    status, first);
     }
 }
 
 // ---- decode -----------------------------------------------------------------------------------
+// byte k of a segment is staged at out[HB_OIDX(phase + k)]: 4 pad bytes after every 128
+#define HB_OIDX(pos) ((pos) + 4u * ((pos) >> 7))
+#define HB_STAGE_BYTES (DC_BATCH_SEG_MAX + 16 + 4 * (DC_BATCH_SEG_MAX / 128 + 1))
+
+// What hb_decode_check and hb_decode_body want of a decode kernel's LDS: lut, scan, bad, and in C
+// the canonical arrays cnt / startv / starti / syms / mn / mx of hb_decode_slow.
 struct HbDecLds {
-    // byte k of the segment at out[HB_OIDX(phase + k)]: 4 pad bytes after every 128
-    __attribute__((aligned(16))) uint8_t out[DC_BATCH_SEG_MAX + 16 + 4 * (DC_BATCH_SEG_MAX / 128 + 1)];
+    __attribute__((aligned(16))) uint8_t out[HB_STAGE_BYTES];
     uint16_t lut[1 << HB_LUT_BITS];   // next 12 bits -> sym | bits << 8; 0: longer, or no code
     HbCode C;
     uint32_t scan[4];
     int bad;
 };
 
-#define HB_OIDX(pos) ((pos) + 4u * ((pos) >> 7))
+struct HbDecArgs {
+    int nary, w;
+    uint32_t S;
+    const uint8_t *mode;
+    const uint32_t *bits;
+    const uint64_t *pay_off;
+    const uint8_t *payload;
+    uint64_t payload_cap;
+    const uint64_t *sync_off;
+    const uint16_t *sync_len;
+    uint64_t sync_cap;
+    uint8_t *out;
+    const uint64_t *out_beg, *out_end;   // (the two may alias: d_out_off, d_out_off + 1)
+    uint64_t out_cap;
+    int32_t *status;
+    unsigned long long *first;
+};
 
-// the symbol whose code leads the 32-bit window `win` (MSB first), by the canonical arrays:
-// its bit length, 0 when no code of lo .. maxbits bits matches (lo: bits the caller has ruled out
-// already are not tested again)
-static __device__ __forceinline__ uint32_t hb_decode_slow(uint32_t win, uint32_t lo, uint32_t maxbits, const HbCode &C,
+// the symbol whose code leads the 32-bit window `win` (MSB first), by the canonical arrays of C
+// (HbCode, or the shared mode's copy of a dc_dtable's): its bit length, 0 when no code of
+// lo .. maxbits bits matches (lo: bits the caller has ruled out already are not tested again).
+// syms is indexed under a mask of its size: HbCode's starti + r is below 256 by construction, a
+// table that another kernel built is not trusted that far.
+template <class Canon>
+static __device__ __forceinline__ uint32_t hb_decode_slow(uint32_t win, uint32_t lo, uint32_t maxbits, const Canon &C,
                                                           int nary, int w, uint32_t &sym)
 {
+    constexpr uint32_t smask = sizeof(C.syms) / sizeof(C.syms[0]) - 1u;
+    static_assert((smask & (smask + 1u)) == 0, "syms holds a power of two of symbols");
     const int top = C.mx;
     if ((nary & (nary - 1)) == 0) {   // n = 2^w: the value of the first L digits is the first L w bits
         int L = C.mn;
@@ -332,7 +378,7 @@ static __device__ __forceinline__ uint32_t hb_decode_slow(uint32_t win, uint32_t
         for (; L <= top && (uint32_t)(L * w) <= maxbits; ++L) {
             const uint32_t r = (win >> (32 - L * w)) - C.startv[L];
             if (r < C.cnt[L]) {
-                sym = C.syms[C.starti[L] + r];
+                sym = C.syms[(C.starti[L] + r) & smask];
                 return (uint32_t)(L * w);
             }
         }
@@ -347,12 +393,149 @@ static __device__ __forceinline__ uint32_t hb_decode_slow(uint32_t win, uint32_t
         if (L >= C.mn && (uint32_t)(L * w) >= lo) {
             const uint32_t r = v - C.startv[L];
             if (r < C.cnt[L]) {
-                sym = C.syms[C.starti[L] + r];
+                sym = C.syms[(C.starti[L] + r) & smask];
                 return (uint32_t)(L * w);
             }
         }
     }
     return 0;
+}
+
+// a segment that passed hb_decode_check
+struct HbSeg {
+    uint32_t len, md, sb, nch;   // output bytes (> 0), mode, bits, chunks
+    uint64_t po, pe, so;         // its payload bytes [po, pe), its first sync entry
+    uint8_t *dptr;               // where its output goes
+};
+
+// Segment i by the threads that call it (tt: the caller's index among them), a workgroup or a
+// wave: every test is uniform among them, and no barrier is reached. Validates the output range,
+// then the cap, then the stream's record, and writes the segment's status; with DC_OK it clears
+// *flag when the caller gives one (a workgroup's commit flag, see hb_decode_body). true: G is a
+// segment for hb_decode_body (false: it failed, or has 0 bytes).
+static __device__ __forceinline__ bool hb_decode_check(const HbDecArgs &A, uint64_t i, uint32_t tt, HbSeg &G, int *flag)
+{
+    const uint32_t S = A.S, slog = (uint32_t)__builtin_ctz(S);
+    const uint64_t oa = A.out_beg[i], ob = A.out_end[i];
+    if (ob < oa || ob - oa > DC_BATCH_SEG_MAX) {
+        if (tt == 0) hb_fail(A.status, A.first, i, DC_E_ARG);
+        return false;
+    }
+    if (ob > A.out_cap) {
+        if (tt == 0) hb_fail(A.status, A.first, i, DC_E_CAPACITY);
+        return false;
+    }
+    const uint32_t len = (uint32_t)(ob - oa);
+    const uint32_t md = A.mode[i], sb = A.bits[i];
+    const uint64_t po = A.pay_off[i], pe = A.pay_off[i + 1], so = A.sync_off[i], se = A.sync_off[i + 1];
+    const uint32_t nch = (len + S - 1) >> slog;
+    bool ok = md <= 1u && sb <= 8u * len && (md == 1u || sb == 8u * len);
+    ok = ok && pe >= po && pe <= A.payload_cap && (po & 15u) == 0 && pe - po == hb_pad16((sb + 7u) >> 3);
+    ok = ok && se >= so && se <= A.sync_cap && se - so == nch;
+    if (!ok) {
+        if (tt == 0) hb_fail(A.status, A.first, i, DC_E_STREAM);
+        return false;
+    }
+    if (tt == 0) {
+        A.status[i] = DC_OK;
+        if (flag) *flag = 0;
+    }
+    G = HbSeg{len, md, sb, nch, po, pe, so, A.out + oa};
+    return len != 0;
+}
+
+// The segment G (number i) staged at `stage`, by the NT threads that hb_decode_check ran on; for
+// a mode-1 segment L.lut and L.C hold its code. The whole workgroup (WAVE false: every barrier
+// below is reached by all of it, every test before one is uniform, and the caller has cleared
+// L.bad, the commit flag, after the barrier that ended the segment before), or one wave (WAVE
+// true: wave-uniform tests, no workgroup barrier, L.bad not used).
+template <bool WAVE, class Lds>
+static __device__ __forceinline__ void hb_decode_body(Lds &L, uint8_t *stage, const HbDecArgs &A, uint64_t i, uint32_t tt,
+                                                      const HbSeg &G)
+{
+    constexpr uint32_t NT = WAVE ? 64u : (uint32_t)HB_THREADS;
+    const uint32_t S = A.S, slog = (uint32_t)__builtin_ctz(S);
+    const uint32_t len = G.len, md = G.md, nch = G.nch;
+    uint8_t *const dptr = G.dptr;
+    const uint32_t phase = (uint32_t)(uintptr_t)dptr & 15u;
+    const uint8_t *const pay = A.payload + G.po;
+    if (md == 0)
+        for (uint32_t k = tt; k < len; k += NT) stage[HB_OIDX(phase + k)] = pay[k];
+    // chunk c by thread c % NT, NT chunks at a time: their bit lengths scanned, then decoded
+    const uint32_t nw = (uint32_t)(G.pe - G.po) / 4;
+    const uint32_t *const pw = reinterpret_cast<const uint32_t *>(pay);
+#define HB_WORD(k) ((k) < nw ? bswap32(pw[k]) : 0u)
+    uint32_t base = 0;
+    int bad = 0;
+    for (uint32_t c0 = 0; c0 < nch; c0 += NT) {
+        const uint32_t c = c0 + tt;
+        const uint32_t clen = c < nch ? A.sync_len[G.so + c] : 0u;
+        uint32_t tot, pos;
+        if (WAVE) {   // (all 64 lanes are here: the loop's bounds are wave-uniform)
+            const uint32_t incl = wave_scan_incl(clen);
+            pos = base + incl - clen;
+            tot = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+        } else {
+            pos = base + wg_scan_excl_u32(clen, L.scan, &tot);
+        }
+        base += tot;
+        if (c >= nch || bad) continue;
+        const uint32_t sym0 = c << slog;
+        const uint32_t cnt = min(S, len - sym0);
+        if (md == 0) {   // stored: 8 bits a symbol
+            bad |= clen != 8u * cnt;
+            continue;
+        }
+        uint32_t k = pos >> 5;
+        const uint32_t sh = pos & 31u;
+        uint64_t win = (((uint64_t)HB_WORD(k) << 32) | HB_WORD(k + 1)) << sh;
+        int wbits = 64 - (int)sh;
+        k += 2;
+        uint32_t used = 0;
+        const uint32_t row = phase + sym0;
+        for (uint32_t j = 0; j < cnt; ++j) {
+            if (wbits < 32) {
+                win |= (uint64_t)HB_WORD(k) << (32 - wbits);
+                ++k;
+                wbits += 32;
+            }
+            const uint32_t e = L.lut[win >> (64 - HB_LUT_BITS)];
+            uint32_t nb = e >> 8, sym = e & 255u;
+            if (!nb) {
+                nb = hb_decode_slow((uint32_t)(win >> 32), HB_LUT_BITS + 1u, 32u, L.C, A.nary, A.w, sym);
+                if (!nb || sym >= 256u) { bad = 1; break; }   // no code, or the code of no byte (a dc_dtable's symbol >= 256)
+            }
+            stage[HB_OIDX(row + j)] = (uint8_t)sym;
+            win <<= nb;
+            wbits -= (int)nb;
+            used += nb;
+        }
+        if (used != clen) bad = 1;
+    }
+#undef HB_WORD
+    bool fail;   // (base: the chunk lengths must sum to bits)
+    if (WAVE) {
+        __builtin_amdgcn_wave_barrier();   // the stage is read by other lanes than wrote it
+        fail = __any(bad || base != G.sb);
+    } else {
+        if (bad || base != G.sb) L.bad = 1;
+        __syncthreads();
+        fail = L.bad != 0;
+    }
+    if (fail) {   // nothing of a corrupt segment is written
+        if (tt == 0) hb_fail(A.status, A.first, i, DC_E_STREAM);
+        return;
+    }
+    // the stage has the destination's 16-B phase: a byte head, aligned 16-B pieces, a byte tail
+    const uint32_t head = min((16u - phase) & 15u, len);
+    if (tt < head) dptr[tt] = stage[HB_OIDX(phase + tt)];
+    const uint32_t nbody = (len - head) >> 4;
+    for (uint32_t v = tt; v < nbody; v += NT) {   // (a piece never crosses a pad: 16 divides 128)
+        const uint32_t *const q = reinterpret_cast<const uint32_t *>(stage + HB_OIDX(phase + head + 16 * v));
+        *reinterpret_cast<uint4 *>(dptr + head + 16 * v) = make_uint4(q[0], q[1], q[2], q[3]);
+    }
+    const uint32_t tail = head + 16 * nbody + tt;
+    if (tail < len) dptr[tail] = stage[HB_OIDX(phase + tail)];
 }
 
 __global__ __launch_bounds__(HB_THREADS) void k_hb_decode(uint64_t count, int nary, int w, uint32_t S,
@@ -367,39 +550,15 @@ __global__ __launch_bounds__(HB_THREADS) void k_hb_decode(uint64_t count, int na
 {
     __shared__ HbDecLds L;
     const int t = threadIdx.x;
-    const uint32_t slog = (uint32_t)__builtin_ctz(S);
+    const HbDecArgs A{nary, w, S, mode, bits, pay_off, payload, payload_cap, sync_off, sync_len, sync_cap,
+                      out, out_beg, out_end, out_cap, status, first};
     for (uint64_t i = blockIdx.x; i < count; i += gridDim.x) {
         __syncthreads();   // the LDS of the segment before
-        const uint64_t oa = out_beg[i], ob = out_end[i];   // (the two may alias: d_out_off, d_out_off + 1)
-        if (ob < oa || ob - oa > DC_BATCH_SEG_MAX) {   // (every test here is workgroup-uniform)
-            if (t == 0) hb_fail(status, first, i, DC_E_ARG);
-            continue;
-        }
-        if (ob > out_cap) {
-            if (t == 0) hb_fail(status, first, i, DC_E_CAPACITY);
-            continue;
-        }
-        const uint32_t len = (uint32_t)(ob - oa);
-        const uint32_t md = mode[i], sb = bits[i];
-        const uint64_t po = pay_off[i], pe = pay_off[i + 1], so = sync_off[i], se = sync_off[i + 1];
-        const uint32_t nch = (len + S - 1) >> slog;
-        bool ok = md <= 1u && sb <= 8u * len && (md == 1u || sb == 8u * len);
-        ok = ok && pe >= po && pe <= payload_cap && (po & 15u) == 0 && pe - po == hb_pad16((sb + 7u) >> 3);
-        ok = ok && se >= so && se <= sync_cap && se - so == nch;
-        if (!ok) {
-            if (t == 0) hb_fail(status, first, i, DC_E_STREAM);
-            continue;
-        }
-        if (t == 0) { status[i] = DC_OK; L.bad = 0; }
-        if (len == 0) continue;
-        uint8_t *const dptr = out + oa;
-        const uint32_t phase = (uint32_t)(uintptr_t)dptr & 15u;
-        const uint8_t *const pay = payload + po;
-        // chunk c by thread c % 256, 256 chunks at a time: their bit lengths scanned in the
-        // workgroup, then decoded (every barrier below is reached by the whole workgroup)
-        if (md == 1u) {
+        HbSeg G;
+        if (!hb_decode_check(A, i, (uint32_t)t, G, &L.bad)) continue;   // (uniform, as every test below)
+        if (G.md == 1u) {   // the table only now: a segment with a bad range or record has its status already
             hb_canonical(L.C, lens + i * 256, nary, w);
-            if (L.C.bad) {   // (uniform: read after hb_canonical's barrier)
+            if (L.C.bad) {   // (read after hb_canonical's barrier)
                 if (t == 0) hb_fail(status, first, i, DC_E_STREAM);
                 continue;
             }
@@ -409,69 +568,8 @@ __global__ __launch_bounds__(HB_THREADS) void k_hb_decode(uint64_t count, int na
                 L.lut[e] = (uint16_t)(nb ? (sym | (nb << 8)) : 0u);
             }
             __syncthreads();
-        } else {
-            for (uint32_t k = t; k < len; k += HB_THREADS) L.out[HB_OIDX(phase + k)] = pay[k];
         }
-        const uint32_t nw = (uint32_t)(pe - po) / 4;
-        const uint32_t *const pw = reinterpret_cast<const uint32_t *>(pay);
-#define HB_WORD(k) ((k) < nw ? bswap32(pw[k]) : 0u)
-        uint32_t base = 0;
-        int bad = 0;
-        for (uint32_t c0 = 0; c0 < nch; c0 += HB_THREADS) {
-            const uint32_t c = c0 + (uint32_t)t;
-            const uint32_t clen = c < nch ? sync_len[so + c] : 0u;
-            uint32_t tot;
-            const uint32_t pos = base + wg_scan_excl_u32(clen, L.scan, &tot);
-            base += tot;
-            if (c >= nch || bad) continue;
-            const uint32_t sym0 = c << slog;
-            const uint32_t cnt = min(S, len - sym0);
-            if (md == 0) {   // stored: 8 bits a symbol
-                bad |= clen != 8u * cnt;
-                continue;
-            }
-            uint32_t k = pos >> 5;
-            const uint32_t sh = pos & 31u;
-            uint64_t win = (((uint64_t)HB_WORD(k) << 32) | HB_WORD(k + 1)) << sh;
-            int wbits = 64 - (int)sh;
-            k += 2;
-            uint32_t used = 0;
-            const uint32_t row = phase + sym0;
-            for (uint32_t j = 0; j < cnt; ++j) {
-                if (wbits < 32) {
-                    win |= (uint64_t)HB_WORD(k) << (32 - wbits);
-                    ++k;
-                    wbits += 32;
-                }
-                const uint32_t e = L.lut[win >> (64 - HB_LUT_BITS)];
-                uint32_t nb = e >> 8, sym = e & 255u;
-                if (!nb) {
-                    nb = hb_decode_slow((uint32_t)(win >> 32), HB_LUT_BITS + 1u, 32u, L.C, nary, w, sym);
-                    if (!nb) { bad = 1; break; }
-                }
-                L.out[HB_OIDX(row + j)] = (uint8_t)sym;
-                win <<= nb;
-                wbits -= (int)nb;
-                used += nb;
-            }
-            if (used != clen) bad = 1;
-        }
-#undef HB_WORD
-        if (bad || base != sb) L.bad = 1;   // (base: the chunk lengths must sum to bits)
-        __syncthreads();
-        if (L.bad) {   // nothing of a corrupt segment is written
-            if (t == 0) hb_fail(status, first, i, DC_E_STREAM);
-            continue;
-        }
-        // the stage has the destination's 16-B phase: a byte head, aligned 16-B pieces, a byte tail
-        const uint32_t head = min((16u - phase) & 15u, len);
-        if ((uint32_t)t < head) dptr[t] = L.out[HB_OIDX(phase + t)];
-        const uint32_t nbody = (len - head) >> 4;
-        for (uint32_t v = t; v < nbody; v += HB_THREADS) {   // (a piece never crosses a pad: 16 divides 128)
-            const uint32_t *const q = reinterpret_cast<const uint32_t *>(L.out + HB_OIDX(phase + head + 16 * v));
-            *reinterpret_cast<uint4 *>(dptr + head + 16 * v) = make_uint4(q[0], q[1], q[2], q[3]);
-        }
-        const uint32_t tail = head + 16 * nbody + (uint32_t)t;
-        if (tail < len) dptr[tail] = L.out[HB_OIDX(phase + tail)];
+        hb_decode_body<false>(L, L.out, A, i, (uint32_t)t, G);
     }
 }
+

@@ -1,20 +1,23 @@
 // dc_batch_shared_kernels.inc -- the shared-table mode of the batched Huffman codec
 // (dc_huff_encode_batch_shared / dc_huff_decode_batch_shared, dc_gpu.h "Huffman batch v1, shared
-// table"); included by dc_core.hip after dc_batch_kernels.inc, whose helpers it uses. One
-// dc_dtable codes every segment, so no work of a segment is proportional to the table: a
-// persistent workgroup copies what it needs of the table into LDS once, before its segment loop.
+// table"); included by dc_core.hip after dc_batch_kernels.inc. One dc_dtable codes every segment,
+// so no work of a segment is proportional to the table: a persistent workgroup copies what it
+// needs of the table into LDS once, before its segment loop. Only what is particular to this
+// mode is here: what a segment takes once the table is in LDS (hb_pack_seg, hb_decode_check,
+// hb_decode_body, hb_decode_slow) is in dc_batch_kernels.inc, the same code as the own-table mode.
 //   k_hbs_plan    nbits[256] in LDS; per segment the sum of nb[byte] and whether a byte has no
 //                 code (no histogram, no table build): mode, bits, and the payload bytes and
 //                 sync entries for the scans
 //   k_scan_u64    twice: pay_off and sync_off
-//   k_hbs_pack    code / nbits in LDS; per segment exactly k_hb_pack's unit scan, LDS stage and
+//   k_hbs_pack    code / nbits in LDS; per segment hb_pack_seg: the unit scan, LDS stage and
 //                 16-B stores
 //   k_hbs_decode  once per workgroup the 12-bit first-level table, filled by code ranges from
 //                 code / nbits (the packed codes are prefix-free bit strings at any arity), and
-//                 the table's canonical arrays for the longer codes; per segment exactly
-//                 k_hb_decode's chunk scan, exactness check and phased output stage. Segments
-//                 are dealt four at a time: four short ones (<= 8 KiB) to the four waves, one
-//                 each, on a quarter of the stage; otherwise one after the other to the workgroup
+//                 the table's canonical arrays for the longer codes; per segment hb_decode_check
+//                 and hb_decode_body: the chunk scan, exactness check and phased output stage.
+//                 Segments are dealt four at a time: four short ones (<= 8 KiB) to the four
+//                 waves, one each, on a quarter of the stage; otherwise one after the other to
+//                 the workgroup
 // The table is read, never written; dec_ready and the dlut* arrays are not touched, so one table
 // serves any number of contexts and streams at once. A table of another arity, or one whose
 // status is neither DC_OK nor DC_E_CODE_TOO_LONG, gives every segment DC_E_ARG.
@@ -100,12 +103,9 @@ __global__ __launch_bounds__(HB_THREADS) void k_hbs_plan(const uint8_t *__restri
 
 // ---- pack -------------------------------------------------------------------------------------
 struct HbsPackLds {
-    __attribute__((aligned(16))) uint32_t stage[DC_BATCH_SEG_MAX / 4];   // the payload, word bit 31 first
-    uint32_t code[256];            // the table's, read once
+    HbPackWork P;
+    uint32_t code[256];   // the table's, read once
     uint32_t nb[256];
-    uint16_t ulen[HB_UNITS_MAX];   // bits per 16-symbol unit
-    uint32_t tbase[HB_THREADS];    // bit offset of unit 16 t
-    uint32_t scan[4];
 };
 
 __global__ __launch_bounds__(HB_THREADS) void k_hbs_pack(const uint8_t *__restrict__ in, const uint64_t *__restrict__ in_off,
@@ -118,7 +118,6 @@ __global__ __launch_bounds__(HB_THREADS) void k_hbs_pack(const uint8_t *__restri
 {
     __shared__ HbsPackLds L;
     const int t = threadIdx.x;
-    const uint32_t slog = (uint32_t)__builtin_ctz(S);
     {
         const uint32_t nb = hbs_nb(T->nbits[t]);
         L.nb[t] = nb;
@@ -127,143 +126,26 @@ __global__ __launch_bounds__(HB_THREADS) void k_hbs_pack(const uint8_t *__restri
     for (uint64_t i = blockIdx.x; i < count; i += gridDim.x) {
         __syncthreads();   // the LDS of the segment before (the first time: the table's copy)
         if (status[i] != DC_OK) continue;   // (DC_E_ARG by the plan; uniform)
-        const uint64_t a = in_off[i];
-        const uint32_t len = (uint32_t)(in_off[i + 1] - a);
-        const uint64_t po = pay_off[i], pe = pay_off[i + 1], so = sync_off[i], se = sync_off[i + 1];
-        if (pe > payload_cap || se > sync_cap) {
-            if (t == 0) hb_fail(status, first, i, DC_E_CAPACITY);
-            continue;
-        }
-        if (len == 0) continue;
-        const uint32_t psz = (uint32_t)(pe - po), nch = (uint32_t)(se - so);
-        const uint8_t *p = in + a;
-        uint4 *const dst = reinterpret_cast<uint4 *>(payload + po);   // (po and payload 16-B aligned)
-        if (mode[i] == 0) {   // stored: the bytes, zero-padded to 16
-            for (uint32_t v = t; v < psz / 16; v += HB_THREADS) {
-                uint32_t q[4];
-                hb_load16(p, 16 * v, len, q);
-                const uint32_t left = len - 16 * v;   // (> 0: psz = pad16(len))
-#pragma unroll
-                for (uint32_t j = 0; j < 4; ++j) {
-                    if (left <= 4 * j) q[j] = 0;
-                    else if (left < 4 * j + 4) q[j] &= (1u << (8 * (left - 4 * j))) - 1u;
-                }
-                dst[v] = make_uint4(q[0], q[1], q[2], q[3]);
-            }
-            for (uint32_t c = t; c < nch; c += HB_THREADS) {
-                const uint32_t left = len - (c << slog);
-                sync_len[so + c] = (uint16_t)(8u * (left < S ? left : S));
-            }
-            continue;
-        }
-        for (uint32_t k = t; k < psz / 4; k += HB_THREADS) L.stage[k] = 0;
-        // unit u (16 symbols) by thread u % 256: its bit length, then the scan (thread t sums
-        // units 16 t .. 16 t + 15), then its codes OR-ed into the stage at its bit offset
-        const uint32_t units = (len + HB_UNIT - 1) / HB_UNIT;
-        for (uint32_t u = t; u < units; u += HB_THREADS) {
-            uint32_t q[4];
-            hb_load16(p, u * HB_UNIT, len, q);
-            const uint32_t cntu = min((uint32_t)HB_UNIT, len - u * HB_UNIT);
-            uint32_t ub = 0;
-#pragma unroll
-            for (uint32_t k = 0; k < HB_UNIT; ++k)
-                if (k < cntu) ub += L.nb[(q[k >> 2] >> (8 * (k & 3))) & 255u];
-            L.ulen[u] = (uint16_t)ub;   // <= 16 * 32
-        }
-        __syncthreads();
-        uint32_t tsum = 0;
-        for (uint32_t u = 16 * (uint32_t)t; u < min(16 * (uint32_t)t + 16, units); ++u) tsum += L.ulen[u];
-        uint32_t total;
-        L.tbase[t] = wg_scan_excl_u32(tsum, L.scan, &total);
-        __syncthreads();
-        {   // the sync index: chunk c = units [c r, (c + 1) r), r = S / 16
-            const uint32_t r = S / HB_UNIT;
-            for (uint32_t c = t; c < nch; c += HB_THREADS) {
-                const uint32_t e = min((c + 1) * r, units);
-                uint32_t cb = 0;
-                for (uint32_t u = c * r; u < e; ++u) cb += L.ulen[u];
-                sync_len[so + c] = (uint16_t)cb;   // <= 1024 * 32
-            }
-        }
-        for (uint32_t u = t; u < units; u += HB_THREADS) {
-            uint32_t pos = L.tbase[u >> 4];
-            for (uint32_t k = u & ~15u; k < u; ++k) pos += L.ulen[k];
-            uint32_t q[4];
-            hb_load16(p, u * HB_UNIT, len, q);
-            const uint32_t cntu = min((uint32_t)HB_UNIT, len - u * HB_UNIT);
-            // a 64-bit accumulator, whole words OR-ed into the stage (neighbours share words)
-            uint32_t wi = pos >> 5, nacc = pos & 31u;
-            uint64_t acc = 0;
-#pragma unroll
-            for (uint32_t k = 0; k < HB_UNIT; ++k) {
-                if (k < cntu) {
-                    const uint32_t b = (q[k >> 2] >> (8 * (k & 3))) & 255u, nb = L.nb[b];
-                    if (nb) acc |= (uint64_t)L.code[b] << (64u - nacc - nb);
-                    nacc += nb;
-                    if (nacc >= 32u) {
-                        if (wi < DC_BATCH_SEG_MAX / 4) atomicOr(&L.stage[wi], (uint32_t)(acc >> 32));
-                        ++wi;
-                        acc <<= 32;
-                        nacc -= 32u;
-                    }
-                }
-            }
-            if (nacc && wi < DC_BATCH_SEG_MAX / 4) atomicOr(&L.stage[wi], (uint32_t)(acc >> 32));
-        }
-        __syncthreads();
-        for (uint32_t v = t; v < psz / 16; v += HB_THREADS) {
-            const uint4 q = reinterpret_cast<const uint4 *>(L.stage)[v];
-            dst[v] = make_uint4(bswap32(q.x), bswap32(q.y), bswap32(q.z), bswap32(q.w));
-        }
+        hb_pack_seg(L.P, L.code, L.nb, i, in, in_off, S, mode, pay_off, payload, payload_cap, sync_off, sync_len, sync_cap,
+                    status, first);
     }
 }
 
 // ---- decode -----------------------------------------------------------------------------------
-struct HbsDecLds {
-    // byte k of the segment at out[HB_OIDX(phase + k)]: 4 pad bytes after every 128
-    __attribute__((aligned(16))) uint8_t out[DC_BATCH_SEG_MAX + 16 + 4 * (DC_BATCH_SEG_MAX / 128 + 1)];
-    uint16_t lut[1 << HB_LUT_BITS];   // next 12 bits -> sym | bits << 8; 0: longer, or no code
-    // the table's canonical arrays (first / count / start / syms), for codes over 12 bits
+// the table's canonical arrays (first / count / start / syms), for codes over 12 bits
+struct HbsCanon {
     uint32_t cnt[DC_MAX_DIGITS + 1], startv[DC_MAX_DIGITS + 1], starti[DC_MAX_DIGITS + 1];
-    uint16_t syms[DC_MAX_SYMS];       // up to 1024 symbols: one >= 256 is never a byte
-    uint32_t scan[4];
-    int mn, mx, bad;
+    uint16_t syms[DC_MAX_SYMS];   // up to 1024 symbols: one >= 256 is never a byte
+    int mn, mx;
 };
 
-// hb_decode_slow on the table's arrays: the symbol (< DC_MAX_SYMS) whose code leads the 32-bit
-// window `win`, its bit length, 0 when no code of lo .. 32 bits matches
-static __device__ __forceinline__ uint32_t hbs_decode_slow(uint32_t win, uint32_t lo, const HbsDecLds &C, int nary, int w,
-                                                           uint32_t &sym)
-{
-    const int top = C.mx;
-    if ((nary & (nary - 1)) == 0) {   // n = 2^w: the value of the first L digits is the first L w bits
-        int L = C.mn;
-        while ((uint32_t)(L * w) < lo) ++L;
-        for (; L <= top && L * w <= 32; ++L) {
-            const uint32_t r = (win >> (32 - L * w)) - C.startv[L];
-            if (r < C.cnt[L]) {
-                sym = C.syms[(C.starti[L] + r) & (DC_MAX_SYMS - 1)];
-                return (uint32_t)(L * w);
-            }
-        }
-        return 0;
-    }
-    uint32_t v = 0;
-    const uint32_t dmask = (1u << w) - 1u;
-    for (int L = 1; L <= top && L * w <= 32; ++L) {
-        const uint32_t d = (win >> (32 - L * w)) & dmask;
-        if (d >= (uint32_t)nary) return 0;
-        v = v * (uint32_t)nary + d;
-        if (L >= C.mn && (uint32_t)(L * w) >= lo) {
-            const uint32_t r = v - C.startv[L];
-            if (r < C.cnt[L]) {
-                sym = C.syms[(C.starti[L] + r) & (DC_MAX_SYMS - 1)];
-                return (uint32_t)(L * w);
-            }
-        }
-    }
-    return 0;
-}
+struct HbsDecLds {   // (the members hb_decode_check and hb_decode_body use, as HbDecLds)
+    __attribute__((aligned(16))) uint8_t out[HB_STAGE_BYTES];
+    uint16_t lut[1 << HB_LUT_BITS];   // next 12 bits -> sym | bits << 8; 0: longer, or no code
+    HbsCanon C;
+    uint32_t scan[4];
+    int bad;
+};
 
 // Segments are dealt four at a time. Four that ask for at most HBS_WAVE_SEG bytes each go to
 // the workgroup's four waves, one each, on a quarter of the stage and without a workgroup
@@ -275,137 +157,16 @@ static __device__ __forceinline__ uint32_t hbs_decode_slow(uint32_t win, uint32_
 static_assert(HBS_WAVE_SEG + 15u + 4u * ((HBS_WAVE_SEG + 15u) >> 7) < HBS_WAVE_STAGE, "a short segment fits a wave's stage");
 static_assert(4u * HBS_WAVE_STAGE <= sizeof(HbsDecLds::out) && HBS_WAVE_STAGE % 16u == 0, "four wave stages in the stage");
 
-struct HbsDecArgs {
-    int nary, w;
-    uint32_t S;
-    const uint8_t *mode;
-    const uint32_t *bits;
-    const uint64_t *pay_off;
-    const uint8_t *payload;
-    uint64_t payload_cap;
-    const uint64_t *sync_off;
-    const uint16_t *sync_len;
-    uint64_t sync_cap;
-    uint8_t *out;
-    const uint64_t *out_beg, *out_end;   // (the two may alias: d_out_off, d_out_off + 1)
-    uint64_t out_cap;
-    int32_t *status;
-    unsigned long long *first;
-};
-
-// segment i by the NT threads that call it (tt: the caller's index among them), staged at
-// `stage`: the whole workgroup (WAVE false: every barrier below is reached by all of it, and every
-// test before one is uniform), or one wave (WAVE true: wave-uniform tests, no workgroup barrier)
+// segment i by one wave (WAVE true) or by the whole workgroup, staged at `stage`. (The workgroup's
+// commit flag is cleared here and not by the check: measured, with that store in the check this
+// kernel's wave path decodes 4 KiB segments 1 % slower, and k_hb_decode 3 % slower without it.)
 template <bool WAVE>
-static __device__ __forceinline__ void hbs_decode_seg(HbsDecLds &L, uint8_t *stage, const HbsDecArgs &A, uint64_t i, uint32_t tt)
+static __device__ __forceinline__ void hbs_decode_seg(HbsDecLds &L, uint8_t *stage, const HbDecArgs &A, uint64_t i, uint32_t tt)
 {
-    constexpr uint32_t NT = WAVE ? 64u : (uint32_t)HB_THREADS;
-    const uint32_t S = A.S, slog = (uint32_t)__builtin_ctz(S);
-    const uint64_t oa = A.out_beg[i], ob = A.out_end[i];
-    if (ob < oa || ob - oa > DC_BATCH_SEG_MAX) {
-        if (tt == 0) hb_fail(A.status, A.first, i, DC_E_ARG);
-        return;
-    }
-    if (ob > A.out_cap) {
-        if (tt == 0) hb_fail(A.status, A.first, i, DC_E_CAPACITY);
-        return;
-    }
-    const uint32_t len = (uint32_t)(ob - oa);
-    const uint32_t md = A.mode[i], sb = A.bits[i];
-    const uint64_t po = A.pay_off[i], pe = A.pay_off[i + 1], so = A.sync_off[i], se = A.sync_off[i + 1];
-    const uint32_t nch = (len + S - 1) >> slog;
-    bool ok = md <= 1u && sb <= 8u * len && (md == 1u || sb == 8u * len);
-    ok = ok && pe >= po && pe <= A.payload_cap && (po & 15u) == 0 && pe - po == hb_pad16((sb + 7u) >> 3);
-    ok = ok && se >= so && se <= A.sync_cap && se - so == nch;
-    if (!ok) {
-        if (tt == 0) hb_fail(A.status, A.first, i, DC_E_STREAM);
-        return;
-    }
-    if (tt == 0) {
-        A.status[i] = DC_OK;
-        if (!WAVE) L.bad = 0;
-    }
-    if (len == 0) return;
-    uint8_t *const dptr = A.out + oa;
-    const uint32_t phase = (uint32_t)(uintptr_t)dptr & 15u;
-    const uint8_t *const pay = A.payload + po;
-    if (md == 0)
-        for (uint32_t k = tt; k < len; k += NT) stage[HB_OIDX(phase + k)] = pay[k];
-    // chunk c by thread c % NT, NT chunks at a time: their bit lengths scanned, then decoded
-    const uint32_t nw = (uint32_t)(pe - po) / 4;
-    const uint32_t *const pw = reinterpret_cast<const uint32_t *>(pay);
-#define HBS_WORD(k) ((k) < nw ? bswap32(pw[k]) : 0u)
-    uint32_t base = 0;
-    int bad = 0;
-    for (uint32_t c0 = 0; c0 < nch; c0 += NT) {
-        const uint32_t c = c0 + tt;
-        const uint32_t clen = c < nch ? A.sync_len[so + c] : 0u;
-        uint32_t tot, pos;
-        if (WAVE) {   // (all 64 lanes are here: the loop's bounds are wave-uniform)
-            const uint32_t incl = wave_scan_incl(clen);
-            pos = base + incl - clen;
-            tot = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-        } else {
-            pos = base + wg_scan_excl_u32(clen, L.scan, &tot);
-        }
-        base += tot;
-        if (c >= nch || bad) continue;
-        const uint32_t sym0 = c << slog;
-        const uint32_t cnt = min(S, len - sym0);
-        if (md == 0) {   // stored: 8 bits a symbol
-            bad |= clen != 8u * cnt;
-            continue;
-        }
-        uint32_t k = pos >> 5;
-        const uint32_t sh = pos & 31u;
-        uint64_t win = (((uint64_t)HBS_WORD(k) << 32) | HBS_WORD(k + 1)) << sh;
-        int wbits = 64 - (int)sh;
-        k += 2;
-        uint32_t used = 0;
-        const uint32_t row = phase + sym0;
-        for (uint32_t j = 0; j < cnt; ++j) {
-            if (wbits < 32) {
-                win |= (uint64_t)HBS_WORD(k) << (32 - wbits);
-                ++k;
-                wbits += 32;
-            }
-            const uint32_t e = L.lut[win >> (64 - HB_LUT_BITS)];
-            uint32_t nb = e >> 8, sym = e & 255u;
-            if (!nb) {
-                nb = hbs_decode_slow((uint32_t)(win >> 32), HB_LUT_BITS + 1u, L, A.nary, A.w, sym);
-                if (!nb || sym >= 256u) { bad = 1; break; }   // no code, or the code of no byte
-            }
-            stage[HB_OIDX(row + j)] = (uint8_t)sym;
-            win <<= nb;
-            wbits -= (int)nb;
-            used += nb;
-        }
-        if (used != clen) bad = 1;
-    }
-#undef HBS_WORD
-    bad |= base != sb;   // (the chunk lengths must sum to bits)
-    if (WAVE) {
-        __builtin_amdgcn_wave_barrier();   // the stage is read by other lanes than wrote it
-        bad = __any(bad);
-    } else {
-        if (bad) L.bad = 1;
-        __syncthreads();
-        bad = L.bad;
-    }
-    if (bad) {   // nothing of a corrupt segment is written
-        if (tt == 0) hb_fail(A.status, A.first, i, DC_E_STREAM);
-        return;
-    }
-    // the stage has the destination's 16-B phase: a byte head, aligned 16-B pieces, a byte tail
-    const uint32_t head = min((16u - phase) & 15u, len);
-    if (tt < head) dptr[tt] = stage[HB_OIDX(phase + tt)];
-    const uint32_t nbody = (len - head) >> 4;
-    for (uint32_t v = tt; v < nbody; v += NT) {   // (a piece never crosses a pad: 16 divides 128)
-        const uint32_t *const q = reinterpret_cast<const uint32_t *>(stage + HB_OIDX(phase + head + 16 * v));
-        *reinterpret_cast<uint4 *>(dptr + head + 16 * v) = make_uint4(q[0], q[1], q[2], q[3]);
-    }
-    const uint32_t tail = head + 16 * nbody + tt;
-    if (tail < len) dptr[tail] = stage[HB_OIDX(phase + tail)];
+    HbSeg G;
+    if (!hb_decode_check(A, i, tt, G, nullptr)) return;
+    if (!WAVE && tt == 0) L.bad = 0;
+    hb_decode_body<WAVE>(L, stage, A, i, tt, G);
 }
 
 __global__ __launch_bounds__(HB_THREADS) void k_hbs_decode(uint64_t count, int nary, int w, uint32_t S,
@@ -425,14 +186,14 @@ __global__ __launch_bounds__(HB_THREADS) void k_hbs_decode(uint64_t count, int n
     if (tok) {   // (uniform) the decode tables, once for every segment of this workgroup
         for (uint32_t e = t; e < (1u << HB_LUT_BITS); e += HB_THREADS) L.lut[e] = 0;
         for (int q = t; q <= DC_MAX_DIGITS; q += HB_THREADS) {
-            L.cnt[q] = T->count[q];
-            L.startv[q] = T->first[q];
-            L.starti[q] = T->start[q];
+            L.C.cnt[q] = T->count[q];
+            L.C.startv[q] = T->first[q];
+            L.C.starti[q] = T->start[q];
         }
-        for (int q = t; q < DC_MAX_SYMS; q += HB_THREADS) L.syms[q] = T->syms[q];
+        for (int q = t; q < DC_MAX_SYMS; q += HB_THREADS) L.C.syms[q] = T->syms[q];
         if (t == 0) {
-            L.mn = max(T->min_len, 1);
-            L.mx = min(T->max_len, DC_MAX_DIGITS);
+            L.C.mn = max(T->min_len, 1);
+            L.C.mx = min(T->max_len, DC_MAX_DIGITS);
         }
         const uint32_t nbt = hbs_nb(T->nbits[t]), codet = T->code[t];
         __syncthreads();
@@ -447,8 +208,8 @@ __global__ __launch_bounds__(HB_THREADS) void k_hbs_decode(uint64_t count, int n
                 if (lo + e < (1u << HB_LUT_BITS)) L.lut[lo + e] = (uint16_t)ent;
         }
     }
-    const HbsDecArgs A{nary, w, S, mode, bits, pay_off, payload, payload_cap, sync_off, sync_len, sync_cap,
-                       out, out_beg, out_end, out_cap, status, first};
+    const HbDecArgs A{nary, w, S, mode, bits, pay_off, payload, payload_cap, sync_off, sync_len, sync_cap,
+                      out, out_beg, out_end, out_cap, status, first};
     const uint64_t groups = (count + 3) / 4;
     for (uint64_t g = blockIdx.x; g < groups; g += gridDim.x) {
         __syncthreads();   // the LDS of the group before (the first time: the tables)

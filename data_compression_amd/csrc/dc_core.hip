@@ -7264,12 +7264,13 @@ uint64_t dc_huff_batch_sync_bound(uint64_t total_bytes, uint64_t count, uint32_t
     return dc_batch_sync_bound_calc(total_bytes, count, S);
 }
 
-static int hbatch_args(dc_ctx *c, const dc_hbatch *b)
+// need_lens: the own-table calls; the shared-table calls read no lens records
+static int hbatch_args(dc_ctx *c, const dc_hbatch *b, bool need_lens)
 {
     if (!c || !b) return DC_E_ARG;
     if (b->n_ary < 2 || b->n_ary > 256 || !sync_ok(b->sync_syms)) return DC_E_ARG;
     if (b->count == 0) return DC_OK;
-    if (!b->d_lens || !b->d_mode || !b->d_bits || !b->d_pay_off || !b->d_sync_off || !b->d_status) return DC_E_ARG;
+    if ((need_lens && !b->d_lens) || !b->d_mode || !b->d_bits || !b->d_pay_off || !b->d_sync_off || !b->d_status) return DC_E_ARG;
     if ((!b->d_payload && b->payload_cap) || (!b->d_sync_len && b->sync_cap)) return DC_E_ARG;
     if (((uintptr_t)b->d_payload) & 15) return DC_E_ARG;
     return DC_OK;
@@ -7282,19 +7283,34 @@ static int hbatch_w(int nary)
     return w;
 }
 
+// What every batch call begins with: d_hb sized for `count` segments (the first-failure slot, then
+// the plan's payload bytes and chunks per segment) and the slot turned over to "no failure".
+static int hbatch_begin(dc_ctx *c, uint64_t count, unsigned long long **first)
+{
+    if (ensure((void **)&c->d_hb, &c->hb_cap, (2 * count + 2) * sizeof(uint64_t))) return DC_E_HIP;
+    *first = reinterpret_cast<unsigned long long *>(c->d_hb);
+    HIPCHK(hipMemsetAsync(*first, 0xFF, sizeof(uint64_t), c->stream));
+    return DC_OK;
+}
+
+// a persistent grid: a workgroup per piece of work, up to the workgroups a 256-CU device holds at
+// once (`cap`, by the kernel's LDS; DC_OPT_BATCH_GRID overrides it)
+static uint64_t hbatch_grid(const dc_ctx *c, uint64_t work, uint64_t cap)
+{
+    if (c->opt_batch_grid) cap = c->opt_batch_grid;
+    return work < cap ? work : cap;
+}
+
 int dc_huff_encode_batch(dc_ctx *c, const uint8_t *d_in, const uint64_t *d_in_off, uint64_t count, const dc_hbatch *b)
 {
-    if (const int r = hbatch_args(c, b)) return r;
+    if (const int r = hbatch_args(c, b, true)) return r;
     if (b->count != count) return DC_E_ARG;
     if (count == 0) return DC_OK;
     if (!d_in_off || count > DC_RANGES_MAX) return DC_E_ARG;
-    if (ensure((void **)&c->d_hb, &c->hb_cap, (2 * count + 2) * sizeof(uint64_t))) return DC_E_HIP;
-    unsigned long long *const first = reinterpret_cast<unsigned long long *>(c->d_hb);
+    unsigned long long *first;
+    if (const int r = hbatch_begin(c, count, &first)) return r;
     uint64_t *const psize = c->d_hb + 2, *const nch = c->d_hb + 2 + count;
-    HIPCHK(hipMemsetAsync(first, 0xFF, sizeof(uint64_t), c->stream));
-    // persistent grids: the workgroups a 256-CU device holds at once (LDS-bound: 3 and 2 per CU)
-    const uint64_t cap3 = c->opt_batch_grid ? c->opt_batch_grid : 768, cap2 = c->opt_batch_grid ? c->opt_batch_grid : 512;
-    const uint64_t g3 = count < cap3 ? count : cap3, g2 = count < cap2 ? count : cap2;
+    const uint64_t g3 = hbatch_grid(c, count, 768), g2 = hbatch_grid(c, count, 512);   // LDS-bound: 3 and 2 per CU
     LAUNCH(c, "hb_plan", k_hb_plan, g3, HB_THREADS, d_in, d_in_off, count, (int)b->n_ary, b->sync_syms, b->d_lens, b->d_mode,
            b->d_bits, psize, nch, b->d_status, first);
     LAUNCH(c, "hb_scan_pay", k_scan_u64, 1, 1024, (const uint64_t *)psize, count, b->d_pay_off);
@@ -7308,15 +7324,13 @@ int dc_huff_encode_batch(dc_ctx *c, const uint8_t *d_in, const uint64_t *d_in_of
 int dc_huff_decode_batch_scatter(dc_ctx *c, const dc_hbatch *b, uint8_t *d_out, const uint64_t *d_out_beg,
                                  const uint64_t *d_out_end, uint64_t out_cap)
 {
-    if (const int r = hbatch_args(c, b)) return r;
+    if (const int r = hbatch_args(c, b, true)) return r;
     const uint64_t count = b->count;
     if (count == 0) return DC_OK;
     if (!d_out_beg || !d_out_end || (!d_out && out_cap) || count > DC_RANGES_MAX) return DC_E_ARG;
-    if (ensure((void **)&c->d_hb, &c->hb_cap, (2 * count + 2) * sizeof(uint64_t))) return DC_E_HIP;
-    unsigned long long *const first = reinterpret_cast<unsigned long long *>(c->d_hb);
-    HIPCHK(hipMemsetAsync(first, 0xFF, sizeof(uint64_t), c->stream));
-    const uint64_t cap2 = c->opt_batch_grid ? c->opt_batch_grid : 512;
-    const uint64_t g2 = count < cap2 ? count : cap2;
+    unsigned long long *first;
+    if (const int r = hbatch_begin(c, count, &first)) return r;
+    const uint64_t g2 = hbatch_grid(c, count, 512);
     LAUNCH(c, "hb_decode", k_hb_decode, g2, HB_THREADS, count, (int)b->n_ary, hbatch_w(b->n_ary), b->sync_syms,
            (const uint8_t *)b->d_lens, (const uint8_t *)b->d_mode, (const uint32_t *)b->d_bits,
            (const uint64_t *)b->d_pay_off, (const uint8_t *)b->d_payload, b->payload_cap, (const uint64_t *)b->d_sync_off,
@@ -7330,32 +7344,20 @@ int dc_huff_decode_batch(dc_ctx *c, const dc_hbatch *b, uint8_t *d_out, const ui
     return dc_huff_decode_batch_scatter(c, b, d_out, d_out_off, d_out_off + 1, out_cap);
 }
 
-// the shared-table mode (dc_batch_shared_kernels.inc): hbatch_args without d_lens, with a table
-static int hbatch_shared_args(dc_ctx *c, const dc_hbatch *b, const dc_dtable *d_table)
-{
-    if (!c || !b || !d_table) return DC_E_ARG;
-    if (b->n_ary < 2 || b->n_ary > 256 || !sync_ok(b->sync_syms)) return DC_E_ARG;
-    if (b->count == 0) return DC_OK;
-    if (!b->d_mode || !b->d_bits || !b->d_pay_off || !b->d_sync_off || !b->d_status) return DC_E_ARG;
-    if ((!b->d_payload && b->payload_cap) || (!b->d_sync_len && b->sync_cap)) return DC_E_ARG;
-    if (((uintptr_t)b->d_payload) & 15) return DC_E_ARG;
-    return DC_OK;
-}
-
+// the shared-table mode (dc_batch_shared_kernels.inc): no d_lens, a table
 int dc_huff_encode_batch_shared(dc_ctx *c, const uint8_t *d_in, const uint64_t *d_in_off, uint64_t count,
                                 const dc_dtable *d_table, const dc_hbatch *b)
 {
-    if (const int r = hbatch_shared_args(c, b, d_table)) return r;
+    if (!d_table) return DC_E_ARG;
+    if (const int r = hbatch_args(c, b, false)) return r;
     if (b->count != count) return DC_E_ARG;
     if (count == 0) return DC_OK;
     if (!d_in_off || count > DC_RANGES_MAX) return DC_E_ARG;
-    if (ensure((void **)&c->d_hb, &c->hb_cap, (2 * count + 2) * sizeof(uint64_t))) return DC_E_HIP;
-    unsigned long long *const first = reinterpret_cast<unsigned long long *>(c->d_hb);
+    unsigned long long *first;
+    if (const int r = hbatch_begin(c, count, &first)) return r;
     uint64_t *const psize = c->d_hb + 2, *const nch = c->d_hb + 2 + count;
-    HIPCHK(hipMemsetAsync(first, 0xFF, sizeof(uint64_t), c->stream));
-    // persistent grids: the plan's LDS is 288 B (4 workgroups a CU), the pack's stage allows 2
-    const uint64_t cap4 = c->opt_batch_grid ? c->opt_batch_grid : 1024, cap2 = c->opt_batch_grid ? c->opt_batch_grid : 512;
-    const uint64_t g4 = count < cap4 ? count : cap4, g2 = count < cap2 ? count : cap2;
+    // the plan's LDS is 288 B (4 workgroups a CU), the pack's stage allows 2
+    const uint64_t g4 = hbatch_grid(c, count, 1024), g2 = hbatch_grid(c, count, 512);
     LAUNCH(c, "hbs_plan", k_hbs_plan, g4, HB_THREADS, d_in, d_in_off, count, (int)b->n_ary, b->sync_syms, d_table, b->d_mode,
            b->d_bits, psize, nch, b->d_status, first);
     LAUNCH(c, "hb_scan_pay", k_scan_u64, 1, 1024, (const uint64_t *)psize, count, b->d_pay_off);
@@ -7369,16 +7371,14 @@ int dc_huff_encode_batch_shared(dc_ctx *c, const uint8_t *d_in, const uint64_t *
 int dc_huff_decode_batch_shared_scatter(dc_ctx *c, const dc_hbatch *b, const dc_dtable *d_table, uint8_t *d_out,
                                         const uint64_t *d_out_beg, const uint64_t *d_out_end, uint64_t out_cap)
 {
-    if (const int r = hbatch_shared_args(c, b, d_table)) return r;
+    if (!d_table) return DC_E_ARG;
+    if (const int r = hbatch_args(c, b, false)) return r;
     const uint64_t count = b->count;
     if (count == 0) return DC_OK;
     if (!d_out_beg || !d_out_end || (!d_out && out_cap) || count > DC_RANGES_MAX) return DC_E_ARG;
-    if (ensure((void **)&c->d_hb, &c->hb_cap, (2 * count + 2) * sizeof(uint64_t))) return DC_E_HIP;
-    unsigned long long *const first = reinterpret_cast<unsigned long long *>(c->d_hb);
-    HIPCHK(hipMemsetAsync(first, 0xFF, sizeof(uint64_t), c->stream));
-    const uint64_t cap2 = c->opt_batch_grid ? c->opt_batch_grid : 512;
-    const uint64_t groups = (count + 3) / 4;   // a workgroup takes four segments at a time
-    const uint64_t g2 = groups < cap2 ? groups : cap2;
+    unsigned long long *first;
+    if (const int r = hbatch_begin(c, count, &first)) return r;
+    const uint64_t g2 = hbatch_grid(c, (count + 3) / 4, 512);   // a workgroup takes four segments at a time
     LAUNCH(c, "hbs_decode", k_hbs_decode, g2, HB_THREADS, count, (int)b->n_ary, hbatch_w(b->n_ary), b->sync_syms, d_table,
            (const uint8_t *)b->d_mode, (const uint32_t *)b->d_bits, (const uint64_t *)b->d_pay_off,
            (const uint8_t *)b->d_payload, b->payload_cap, (const uint64_t *)b->d_sync_off, (const uint16_t *)b->d_sync_len,

@@ -438,7 +438,9 @@ int dc_huff_batch_status(dc_ctx *ctx);
  * three calls are asynchronous and make no host read; count 0 returns DC_OK without a launch;
  * dc_huff_batch_status answers for them; DC_OPT_BATCH_GRID sizes their grids. Encode: one plan
  * kernel (no histogram, no table work), the two scans, one pack kernel. Decode: one launch, the
- * first-level table and the long-code arrays built once per workgroup, not per segment. */
+ * first-level table and the long-code arrays built once per workgroup, not per segment. Once a
+ * segment's table is in LDS, its pack and its decode (validation, chunk checks, commit, write) are
+ * the same device code in both modes (csrc/dc_batch_kernels.inc). */
 int dc_huff_encode_batch_shared(dc_ctx *ctx, const uint8_t *d_in, const uint64_t *d_in_off, uint64_t count,
                                 const dc_dtable *d_table, const dc_hbatch *batch);
 int dc_huff_decode_batch_shared(dc_ctx *ctx, const dc_hbatch *batch, const dc_dtable *d_table,

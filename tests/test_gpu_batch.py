@@ -73,11 +73,12 @@ def _gapped(segs, lead=3, gap=5):
     return np.array(starts, np.int64), at + 31
 
 
-def _check_decode(torch, codec, enc, segs, tag, bad=None):
-    """ONE decode_batch into a 0xA5 buffer at gapped, odd offsets: every segment not in `bad`
-    (index -> expected status) equals its input, every other byte is untouched."""
+def _check_decode(torch, codec, enc, segs, tag, bad=None, cap=None):
+    """ONE decode_batch into a 0xA5 buffer (of `cap` bytes) at gapped, odd offsets: every segment
+    not in `bad` (index -> expected status) equals its input, every other byte is untouched."""
     bad = bad or {}
-    starts, cap = _gapped(segs)
+    starts, full = _gapped(segs)
+    cap = full if cap is None else cap
     out = torch.full((cap,), FILL, dtype=torch.uint8, device="cuda")
     codec.decode_batch(enc, out=out, out_off=starts)
     st = enc["status"].cpu().numpy()
@@ -229,21 +230,45 @@ def test_payload_cap_inside_a_segment(torch_cuda, codec):
     _check_decode(torch_cuda, codec, enc, segs, ("cap",), bad={2: DC_E_STREAM, 3: DC_E_STREAM})
 
 
-@pytest.mark.parametrize("what", ("lens", "sync_len", "mode"))
+def _corrupt_lens(enc, seg, k, length):
+    """A copy of enc in which segment k's most frequent symbol has `length` digits."""
+    sym = int(np.bincount(seg, minlength=256).argmax())
+    assert int(enc["mode"][k]) == 1 and int(enc["lens"][k, sym]) > 0
+    enc = dict(enc, lens=enc["lens"].clone())
+    enc["lens"][k, sym] = length
+    return enc
+
+
+# lens: a present symbol loses its code; 200: a length over DC_MAX_DIGITS, 33: a code over 32 bits
+# (n = 2), the two records the canonical build itself rejects
+@pytest.mark.parametrize("what", ("lens", "lens_200", "lens_33", "sync_len", "mode"))
 def test_a_corrupt_segment_fails_alone(torch_cuda, codec, what):
     torch = torch_cuda
     segs = [SEGMENTS[8], SEGMENTS[10], SEGMENTS[9], SEGMENTS[6]]
     enc, x, off = _encode(torch, codec, segs)
     k = 1
     assert int(enc["mode"][k]) == 1
-    enc = dict(enc)
-    enc[what] = enc[what].clone()
-    if what == "lens":     # a present symbol loses its code
-        sym = int(np.bincount(segs[k], minlength=256).argmax())
-        assert int(enc["lens"][k, sym]) > 0
-        enc["lens"][k, sym] = 0
-    elif what == "sync_len":
-        enc["sync_len"][int(enc["sync_off"][k]) + 3] += 1
+    if what.startswith("lens"):
+        enc = _corrupt_lens(enc, segs[k], k, {"lens": 0, "lens_200": 200, "lens_33": 33}[what])
     else:
-        enc["mode"][k] = 7
+        enc = dict(enc)
+        enc[what] = enc[what].clone()
+        if what == "sync_len":
+            enc["sync_len"][int(enc["sync_off"][k]) + 3] += 1
+        else:
+            enc["mode"][k] = 7
     _check_decode(torch, codec, enc, segs, (what,), bad={k: DC_E_STREAM})
+
+
+def test_a_bad_output_range_is_reported_before_a_bad_lens_record(torch_cuda, codec):
+    """A segment whose output ends past out_cap AND whose lens record the canonical build rejects
+    is DC_E_CAPACITY: the range is validated before the record is read."""
+    torch = torch_cuda
+    segs = [SEGMENTS[8], SEGMENTS[10], SEGMENTS[9], SEGMENTS[6]]
+    enc, x, off = _encode(torch, codec, segs)
+    k = 3
+    enc = _corrupt_lens(enc, segs[k], k, 200)
+    starts, _ = _gapped(segs)
+    cap = int(starts[k]) + 100   # ends inside segment k's output
+    assert cap < starts[k] + segs[k].size
+    _check_decode(torch, codec, enc, segs, ("precedence",), bad={k: DC_E_CAPACITY}, cap=cap)
