@@ -132,6 +132,10 @@ def _declare_core(L):
         "dc_huff_decode_batch_shared": ([vp, C.POINTER(HBatch), P, P, P, u64], i32),
         "dc_huff_decode_batch_shared_scatter": ([vp, C.POINTER(HBatch), P, P, P, P, u64], i32),
         "dc_huff_table_get_lengths": ([vp, P, C.POINTER(C.c_int32), i32, C.POINTER(i32)], i32),
+        "dc_huff_batch_range_chunks": ([u64, u64, u32, C.POINTER(u64), C.POINTER(u64)], i32),
+        "dc_huff_batch_range_args": ([u64, u64, u64, u64, u64, u64], i32),
+        "dc_huff_decode_batch_ranges": ([vp, C.POINTER(HBatch), P, P, P, P, P, u64, P, u64, P], i32),
+        "dc_huff_decode_batch_shared_ranges": ([vp, C.POINTER(HBatch), P, P, P, P, P, P, u64, P, u64, P], i32),
         "dc_huff_decode_redo_count": ([vp, C.POINTER(u64)], i32),
         "dc_huff_base64url": ([vp, P, u64, u64, P], i32),
         "dc_huff_text_bits": ([i32, i32], i32),

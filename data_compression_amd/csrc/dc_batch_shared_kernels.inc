@@ -147,6 +147,37 @@ struct HbsDecLds {   // (the members hb_decode_check and hb_decode_body use, as 
     int bad;
 };
 
+// The decode tables of *T in L (lut and C), by the whole workgroup (t: threadIdx.x, its lane and
+// wave), once for every segment or range it takes: k_hbs_decode and k_hbs_decode_ranges
+// (dc_batch_range_kernels.inc). The caller's next barrier ends the fill.
+static __device__ __forceinline__ void hbs_tables_load(HbsDecLds &L, const dc_dtable *__restrict__ T, int t, uint32_t lane,
+                                                       uint32_t wave)
+{
+    for (uint32_t e = t; e < (1u << HB_LUT_BITS); e += HB_THREADS) L.lut[e] = 0;
+    for (int q = t; q <= DC_MAX_DIGITS; q += HB_THREADS) {
+        L.C.cnt[q] = T->count[q];
+        L.C.startv[q] = T->first[q];
+        L.C.starti[q] = T->start[q];
+    }
+    for (int q = t; q < DC_MAX_SYMS; q += HB_THREADS) L.C.syms[q] = T->syms[q];
+    if (t == 0) {
+        L.C.mn = max(T->min_len, 1);
+        L.C.mx = min(T->max_len, DC_MAX_DIGITS);
+    }
+    const uint32_t nbt = hbs_nb(T->nbits[t]), codet = T->code[t];
+    __syncthreads();
+    // byte s of a code of nb <= 12 bits owns the windows [code << (12 - nb), (code + 1) << (12 - nb)):
+    // wave v takes bytes 64 v .. 64 v + 63 in turn, its lanes a range's entries
+    for (int j = 0; j < 64; ++j) {
+        const uint32_t nb = (uint32_t)__shfl((int)nbt, j, 64), code = (uint32_t)__shfl((int)codet, j, 64);
+        if (nb == 0 || nb > HB_LUT_BITS) continue;   // (wave-uniform)
+        const uint32_t lo = code << (HB_LUT_BITS - nb), span = 1u << (HB_LUT_BITS - nb);
+        const uint32_t ent = (64u * wave + (uint32_t)j) | (nb << 8);
+        for (uint32_t e = lane; e < span; e += 64)
+            if (lo + e < (1u << HB_LUT_BITS)) L.lut[lo + e] = (uint16_t)ent;
+    }
+}
+
 // Segments are dealt four at a time. Four that ask for at most HBS_WAVE_SEG bytes each go to
 // the workgroup's four waves, one each, on a quarter of the stage and without a workgroup
 // barrier: a 4 KiB segment has 64 chunks at S = 64, which keep one wave busy and would leave the
@@ -183,31 +214,7 @@ __global__ __launch_bounds__(HB_THREADS) void k_hbs_decode(uint64_t count, int n
     const int t = threadIdx.x;
     const uint32_t lane = (uint32_t)t & 63u, wave = (uint32_t)t >> 6;
     const bool tok = hbs_table_ok(T, nary);
-    if (tok) {   // (uniform) the decode tables, once for every segment of this workgroup
-        for (uint32_t e = t; e < (1u << HB_LUT_BITS); e += HB_THREADS) L.lut[e] = 0;
-        for (int q = t; q <= DC_MAX_DIGITS; q += HB_THREADS) {
-            L.C.cnt[q] = T->count[q];
-            L.C.startv[q] = T->first[q];
-            L.C.starti[q] = T->start[q];
-        }
-        for (int q = t; q < DC_MAX_SYMS; q += HB_THREADS) L.C.syms[q] = T->syms[q];
-        if (t == 0) {
-            L.C.mn = max(T->min_len, 1);
-            L.C.mx = min(T->max_len, DC_MAX_DIGITS);
-        }
-        const uint32_t nbt = hbs_nb(T->nbits[t]), codet = T->code[t];
-        __syncthreads();
-        // byte s of a code of nb <= 12 bits owns the windows [code << (12 - nb), (code + 1) << (12 - nb)):
-        // wave v takes bytes 64 v .. 64 v + 63 in turn, its lanes a range's entries
-        for (int j = 0; j < 64; ++j) {
-            const uint32_t nb = (uint32_t)__shfl((int)nbt, j, 64), code = (uint32_t)__shfl((int)codet, j, 64);
-            if (nb == 0 || nb > HB_LUT_BITS) continue;   // (wave-uniform)
-            const uint32_t lo = code << (HB_LUT_BITS - nb), span = 1u << (HB_LUT_BITS - nb);
-            const uint32_t ent = (64u * wave + (uint32_t)j) | (nb << 8);
-            for (uint32_t e = lane; e < span; e += 64)
-                if (lo + e < (1u << HB_LUT_BITS)) L.lut[lo + e] = (uint16_t)ent;
-        }
-    }
+    if (tok) hbs_tables_load(L, T, t, lane, wave);   // (uniform) the decode tables, once for every segment of this workgroup
     const HbDecArgs A{nary, w, S, mode, bits, pay_off, payload, payload_cap, sync_off, sync_len, sync_cap,
                       out, out_beg, out_end, out_cap, status, first};
     const uint64_t groups = (count + 3) / 4;

@@ -18,6 +18,7 @@
 
 #include "dc_gpu.h"
 #include "dc_batch_bound.h"
+#include "dc_batch_range.h"
 
 #define DC_VERSION "dc-mi355x 0.1 (gfx950)"
 #define DC_SYNC_GROUP 64
@@ -6268,6 +6269,7 @@ __global__ __launch_bounds__(256) void k_copy_probe(const uint4 *__restrict__ sr
 #include "dc_range_kernels.inc"
 #include "dc_batch_kernels.inc"
 #include "dc_batch_shared_kernels.inc"
+#include "dc_batch_range_kernels.inc"
 
 #ifdef DC_AB_KERNELS
 #include "dc_ab_kernels.inc"
@@ -7391,6 +7393,71 @@ int dc_huff_decode_batch_shared(dc_ctx *c, const dc_hbatch *b, const dc_dtable *
 {
     if (b && b->count && !d_out_off) return DC_E_ARG;
     return dc_huff_decode_batch_shared_scatter(c, b, d_table, d_out, d_out_off, d_out_off + 1, out_cap);
+}
+
+// the range arithmetic (dc_batch_range.h), as the kernels compile it
+int dc_huff_batch_range_chunks(uint64_t first, uint64_t count, uint32_t S, uint64_t *c_lo, uint64_t *c_hi)
+{
+    if (!c_lo || !c_hi || !sync_ok(S)) return DC_E_ARG;
+    dc_batch_range_chunks(first, count, S, c_lo, c_hi);
+    return DC_OK;
+}
+int dc_huff_batch_range_args(uint64_t seg_beg, uint64_t seg_end, uint64_t first, uint64_t count, uint64_t out_off,
+                             uint64_t out_cap)
+{
+    uint32_t len = 0;
+    if (const int r = dc_batch_range_seg_len(seg_beg, seg_end, DC_BATCH_SEG_MAX, &len)) return r;
+    return dc_batch_range_args(len, first, count, out_off, out_cap);
+}
+
+// byte ranges of segments (dc_batch_range_kernels.inc). What both calls begin with, after
+// hbatch_args: 1 (nothing to do), 0 with the first-failure slot turned over, or an error.
+static int hbatch_ranges_begin(dc_ctx *c, const uint64_t *d_seg_off, const uint64_t *d_seg, const uint64_t *d_first,
+                               const uint64_t *d_count, const uint64_t *d_out_off, uint64_t nranges, const uint8_t *d_out,
+                               uint64_t out_cap, const int32_t *d_rstatus, unsigned long long **first)
+{
+    if (nranges == 0) return 1;
+    if (!d_seg_off || !d_seg || !d_first || !d_count || !d_out_off || !d_rstatus || (!d_out && out_cap)) return DC_E_ARG;
+    if (nranges > DC_RANGES_MAX) return DC_E_ARG;
+    return hbatch_begin(c, 0, first);   // (the slot alone: no plan arrays)
+}
+
+int dc_huff_decode_batch_ranges(dc_ctx *c, const dc_hbatch *b, const uint64_t *d_seg_off, const uint64_t *d_seg,
+                                const uint64_t *d_first, const uint64_t *d_count, const uint64_t *d_out_off,
+                                uint64_t nranges, uint8_t *d_out, uint64_t out_cap, int32_t *d_rstatus)
+{
+    if (const int r = hbatch_args(c, b, true)) return r;
+    unsigned long long *first;
+    if (const int r = hbatch_ranges_begin(c, d_seg_off, d_seg, d_first, d_count, d_out_off, nranges, d_out, out_cap, d_rstatus,
+                                          &first))
+        return r > 0 ? DC_OK : r;
+    const HbRangeArgs R{d_seg_off, d_seg, d_first, d_count, d_out_off, b->count};
+    const uint64_t g2 = hbatch_grid(c, nranges, 512);   // LDS-bound: 2 per CU
+    LAUNCH(c, "hb_decode_ranges", k_hb_decode_ranges, g2, HB_THREADS, R, nranges, (int)b->n_ary, hbatch_w(b->n_ary),
+           b->sync_syms, (const uint8_t *)b->d_lens, (const uint8_t *)b->d_mode, (const uint32_t *)b->d_bits,
+           (const uint64_t *)b->d_pay_off, (const uint8_t *)b->d_payload, b->payload_cap, (const uint64_t *)b->d_sync_off,
+           (const uint16_t *)b->d_sync_len, b->sync_cap, d_out, out_cap, d_rstatus, first);
+    return DC_OK;
+}
+
+int dc_huff_decode_batch_shared_ranges(dc_ctx *c, const dc_hbatch *b, const dc_dtable *d_table, const uint64_t *d_seg_off,
+                                       const uint64_t *d_seg, const uint64_t *d_first, const uint64_t *d_count,
+                                       const uint64_t *d_out_off, uint64_t nranges, uint8_t *d_out, uint64_t out_cap,
+                                       int32_t *d_rstatus)
+{
+    if (!d_table) return DC_E_ARG;
+    if (const int r = hbatch_args(c, b, false)) return r;
+    unsigned long long *first;
+    if (const int r = hbatch_ranges_begin(c, d_seg_off, d_seg, d_first, d_count, d_out_off, nranges, d_out, out_cap, d_rstatus,
+                                          &first))
+        return r > 0 ? DC_OK : r;
+    const HbRangeArgs R{d_seg_off, d_seg, d_first, d_count, d_out_off, b->count};
+    const uint64_t g2 = hbatch_grid(c, (nranges + 3) / 4, 512);   // a workgroup takes four ranges at a time
+    LAUNCH(c, "hbs_decode_ranges", k_hbs_decode_ranges, g2, HB_THREADS, R, nranges, (int)b->n_ary, hbatch_w(b->n_ary),
+           b->sync_syms, d_table, (const uint8_t *)b->d_mode, (const uint32_t *)b->d_bits, (const uint64_t *)b->d_pay_off,
+           (const uint8_t *)b->d_payload, b->payload_cap, (const uint64_t *)b->d_sync_off, (const uint16_t *)b->d_sync_len,
+           b->sync_cap, d_out, out_cap, d_rstatus, first);
+    return DC_OK;
 }
 
 int dc_huff_table_get_lengths(dc_ctx *c, const dc_dtable *d_table, int32_t *h_lengths, int max_entries, int *h_count)

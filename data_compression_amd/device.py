@@ -459,6 +459,49 @@ class Codec:
             raise ValueError(f"{what} output: contiguous uint8")
         return out
 
+    def _range_lists(self, what, lists, out, out_off):
+        """The gather lists of decode_ranges / decode_batch_ranges: `lists` is (name, value) pairs
+        ending with count, each an int64 device tensor or a Python sequence; out_off defaults to
+        the exclusive cumulative sum of count (computed on the device), out to a new tensor that
+        holds every range (sized with one host read unless count is a sequence and out_off the
+        default). Returns (device tensors of lists, out_off, out, the buffer out is a view of)."""
+        dev = f"cuda:{self.device}"
+
+        def as_dev(v, name):
+            if hasattr(v, "data_ptr"):
+                if v.dtype != torch.int64 or not v.is_cuda or not v.is_contiguous():
+                    raise ValueError(f"{what} {name}: a contiguous int64 device tensor")
+                return v
+            a = np.ascontiguousarray(v, dtype=np.int64).reshape(-1)
+            if a.size and a.min() < 0:
+                raise ValueError(f"{what} {name}: non-negative values")
+            return torch.from_numpy(a).to(dev)
+
+        names = [n for n, _ in lists]
+        count = lists[-1][1]
+        total = None   # bytes of a packed output, when the host knows the counts
+        if out_off is None and not hasattr(count, "data_ptr"):
+            total = int(np.asarray(count, dtype=np.int64).sum())
+        tensors = [as_dev(v, n) for n, v in lists]
+        count = tensors[-1]
+        nr = count.numel()
+        if any(t.numel() != nr for t in tensors):
+            raise ValueError(f"{what}: {', '.join(names[:-1])} and {names[-1]} differ in length")
+        if out_off is None:
+            out_off = torch.cumsum(count, 0) - count
+        else:
+            out_off = as_dev(out_off, "out_off")
+            if out_off.numel() != nr:
+                raise ValueError(f"{what}: out_off and count differ in length")
+        if out is None:
+            if total is None:
+                total = int((out_off + count).max().item()) if nr else 0
+            buf = self._t(max(total, 1))
+            out = buf[: max(total, 0)]
+        else:
+            buf = self._u8_out(out, what)
+        return tensors, out_off, out, buf
+
     def decode_range(self, enc, first: int, count: int, out=None):
         """Symbols [first, first + count) of the stream enc (the dict of encode() /
         small_huff_encode()) -> a uint8 device tensor of count bytes (a view of `out` when
@@ -485,38 +528,9 @@ class Codec:
         (out, out_off). A range past the stream or past out writes nothing and makes
         decode_status() DC_E_ARG (-1); the other ranges are decoded."""
         stream = self._range_stream(enc)
-        dev = f"cuda:{self.device}"
-
-        def as_dev(v, name):
-            if hasattr(v, "data_ptr"):
-                if v.dtype != torch.int64 or not v.is_cuda or not v.is_contiguous():
-                    raise ValueError(f"decode_ranges {name}: a contiguous int64 device tensor")
-                return v
-            a = np.ascontiguousarray(v, dtype=np.int64).reshape(-1)
-            if a.size and a.min() < 0:
-                raise ValueError(f"decode_ranges {name}: non-negative values")
-            return torch.from_numpy(a).to(dev)
-
-        total = None   # bytes of a packed output, when the host knows the counts
-        if out_off is None and not hasattr(count, "data_ptr"):
-            total = int(np.asarray(count, dtype=np.int64).sum())
-        first, count = as_dev(first, "first"), as_dev(count, "count")
+        (first, count), out_off, out, buf = self._range_lists(
+            "decode_ranges", (("first", first), ("count", count)), out, out_off)
         nr = count.numel()
-        if first.numel() != nr:
-            raise ValueError("decode_ranges: first and count differ in length")
-        if out_off is None:
-            out_off = torch.cumsum(count, 0) - count
-        else:
-            out_off = as_dev(out_off, "out_off")
-            if out_off.numel() != nr:
-                raise ValueError("decode_ranges: out_off and count differ in length")
-        if out is None:
-            if total is None:
-                total = int((out_off + count).max().item()) if nr else 0
-            buf = self._t(max(total, 1))
-            out = buf[: max(total, 0)]
-        else:
-            buf = self._u8_out(out, "decode_ranges")
         check("dc_huff_decode_ranges", self.L.dc_huff_decode_ranges(self.ctx, *stream, _ptr(first), _ptr(count),
                                                                     _ptr(out_off), nr, _ptr(buf), out.numel()))
         return out, out_off
@@ -619,6 +633,31 @@ class Codec:
             fn = "dc_huff_decode_batch_scatter" if table is None else "dc_huff_decode_batch_shared_scatter"
             check(fn, getattr(self.L, fn)(self.ctx, C.byref(b), *tab, _ptr(buf), _ptr(out_off), _ptr(end), buf.numel()))
         return out, out_off
+
+    def decode_batch_ranges(self, enc, seg, first, count, out=None, out_off=None):
+        """Byte ranges of segments in one call (dc_huff_decode_batch_ranges, or
+        dc_huff_decode_batch_shared_ranges when enc has a "table"): range r = bytes [first[r],
+        first[r] + count[r]) of segment seg[r] of the dict encode_batch returned -> out[out_off[r]
+        ..). seg / first / count / out_off: int64 device tensors (read by the kernels: a gather
+        list computed on the GPU is used as it is) or Python sequences. enc["offsets"] gives the
+        segment lengths. out_off defaults to the exclusive cumulative sum of count, computed on
+        the device (the ranges packed back to back); out defaults to a new tensor that holds every
+        range (sized with one host read unless count is a Python sequence and out_off the
+        default). Asynchronous, one launch. Returns (out, out_off, status): status[r] (int32,
+        device) is range r's outcome, batch_status() the lowest failing range's. A failing range
+        writes nothing and never stops the others. Only the chunks a range touches are read and
+        verified."""
+        (seg, first, count), out_off, out, buf = self._range_lists(
+            "decode_batch_ranges", (("seg", seg), ("first", first), ("count", count)), out, out_off)
+        nr = count.numel()
+        status = self._t(max(nr, 1), torch.int32)[:nr]
+        b = self._hbatch(enc, enc["payload_cap"], enc["sync_cap"])
+        table = enc.get("table")
+        tab = () if table is None else (_ptr(table),)
+        fn = "dc_huff_decode_batch_ranges" if table is None else "dc_huff_decode_batch_shared_ranges"
+        check(fn, getattr(self.L, fn)(self.ctx, C.byref(b), *tab, _ptr(enc["offsets"]), _ptr(seg), _ptr(first), _ptr(count),
+                                      _ptr(out_off), nr, _ptr(buf), out.numel(), _ptr(status)))
+        return out, out_off, status
 
     def batch_table(self, x, n_ary: int = 2):
         """The table of the whole input x (device uint8): hist plus table, for

@@ -452,6 +452,65 @@ int dc_huff_decode_batch_shared_scatter(dc_ctx *ctx, const dc_hbatch *batch, con
  * back): all a shared batch needs stored beside its arrays. *h_count receives max_symbol_value + 1;
  * DC_E_CAPACITY (nothing copied) when max_entries is smaller. Synchronising. */
 int dc_huff_table_get_lengths(dc_ctx *ctx, const dc_dtable *d_table, int32_t *h_lengths, int max_entries, int *h_count);
+/* ---- Huffman batch v1: byte ranges of segments in one call ------------------------------------
+ * Random access into a batch by its per-chunk u16 bit lengths, with no change to the format.
+ * Range r is the bytes [d_first[r], d_first[r] + d_count[r]) of segment d_seg[r]; it goes to
+ * d_out[d_out_off[r] .. d_out_off[r] + d_count[r]), at any byte alignment. d_seg_off (batch->count
+ * + 1 entries) gives the segment lengths as d_in_off did at encode (the format does not store
+ * them); only the differences d_seg_off[i + 1] - d_seg_off[i] are used. Every array is a device
+ * u64 array that the kernels read, so a gather list computed on the GPU works as it is. None of
+ * them may be written while the call runs.
+ * dc_huff_decode_batch_ranges is for a batch of own tables (d_lens), dc_huff_decode_batch_shared_
+ * ranges for one coded under *d_table (d_lens is not read).
+ * Asynchronous, no host read, one launch whatever nranges is. nranges 0 returns DC_OK without a
+ * launch; nranges > DC_RANGES_MAX returns DC_E_ARG. Host argument rules are the whole-segment
+ * decoders'; in addition d_seg_off, the four range arrays and d_rstatus must not be NULL when
+ * nranges > 0. batch->d_status is neither read nor written.
+ * d_rstatus[r] (i32, nranges entries) receives the range's outcome; a bad range never stops the
+ * others. The tests run in this order, and the first that fails decides:
+ *   1  DC_E_ARG       d_seg[r] >= batch->count
+ *   2  DC_E_ARG       the segment's offsets decrease, or its length len exceeds DC_BATCH_SEG_MAX
+ *   3  DC_E_ARG       first > len or count > len - first (no sum is formed: first = 2^64 - 1 with
+ *                     count = 2 is refused, not wrapped)
+ *   4  DC_E_CAPACITY  out_off > out_cap or count > out_cap - out_off
+ *   5  DC_OK          count == 0: nothing further is read
+ *   6  DC_E_ARG       (shared) the table's arity is not the batch's, or its status is neither
+ *                     DC_OK nor DC_E_CODE_TOO_LONG: every range that comes this far
+ *      DC_E_STREAM    the segment's record fails the whole-segment decoder's tests against len
+ *                     (mode, bits, pay_off, sync_off), or (own tables) its lens give no code
+ *   7  DC_E_STREAM    a touched chunk does not decode to exactly its symbols in exactly its bits,
+ *                     a stored segment's touched entry is not 8 x its symbols, or the last
+ *                     touched chunk ends past bits
+ * A range with any status but DC_OK writes no byte, and no byte of d_out outside the requested
+ * ranges is ever written. Output ranges that overlap are the caller's business.
+ * What is read and verified: only the chunks a range touches, plus the u16 entries of the
+ * segment's chunks before them (at most 4096 entries, 8 KiB), summed for the first touched
+ * chunk's bit position. Corruption elsewhere in the segment is NOT seen by a range read: only a
+ * whole-segment decode checks that the chunk lengths sum to bits and that every chunk decodes.
+ * The context's first-failure slot keeps the lowest failing range index: dc_huff_batch_status
+ * answers for these calls as for the others. DC_OPT_BATCH_GRID sizes their grids.
+ * Cost. Shared table: the tables are copied once per workgroup; ranges are dealt four consecutive
+ * at a time, four of at most 8 KiB each one to a wave, a group with a longer range one after the
+ * other to the workgroup. Own tables: each workgroup takes a contiguous run of range indices and
+ * rebuilds the segment's code (from its 256 lens) only when d_seg[r] differs from the range
+ * before, so a list sorted by segment pays one table build per segment (per workgroup that meets
+ * it) and an unsorted list pays one per range. */
+/* The range arithmetic as the kernels compile it (csrc/dc_batch_range.h), pure host code, for a
+ * caller that plans or checks a gather list on the host. dc_huff_batch_range_chunks: the chunks
+ * [*c_lo, *c_hi) of sync_syms symbols that hold a byte of [first, first + count) (count 0: none,
+ * c_lo == c_hi); DC_E_ARG for a NULL pointer or an invalid sync_syms. dc_huff_batch_range_args:
+ * tests 2 to 4 above for a segment of offsets [seg_beg, seg_end): DC_E_ARG, DC_E_CAPACITY or DC_OK. */
+int dc_huff_batch_range_chunks(uint64_t first, uint64_t count, uint32_t sync_syms, uint64_t *c_lo, uint64_t *c_hi);
+int dc_huff_batch_range_args(uint64_t seg_beg, uint64_t seg_end, uint64_t first, uint64_t count, uint64_t out_off,
+                             uint64_t out_cap);
+int dc_huff_decode_batch_ranges(dc_ctx *ctx, const dc_hbatch *batch, const uint64_t *d_seg_off,
+                                const uint64_t *d_seg, const uint64_t *d_first, const uint64_t *d_count,
+                                const uint64_t *d_out_off, uint64_t nranges, uint8_t *d_out, uint64_t out_cap,
+                                int32_t *d_rstatus);
+int dc_huff_decode_batch_shared_ranges(dc_ctx *ctx, const dc_hbatch *batch, const dc_dtable *d_table,
+                                       const uint64_t *d_seg_off, const uint64_t *d_seg, const uint64_t *d_first,
+                                       const uint64_t *d_count, const uint64_t *d_out_off, uint64_t nranges,
+                                       uint8_t *d_out, uint64_t out_cap, int32_t *d_rstatus);
 
 /* base64url text (6 bits per char, MSB-first) of bits [bit_base, bit_base+bits) */
 int dc_huff_base64url(dc_ctx *ctx, const uint32_t *d_words, uint64_t bit_base, uint64_t bits,

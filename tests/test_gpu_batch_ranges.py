@@ -1,0 +1,240 @@
+"""Byte ranges of batch segments on the device: dc_huff_decode_batch_ranges /
+dc_huff_decode_batch_shared_ranges (k_hb_decode_ranges, k_hbs_decode_ranges) through
+Codec.decode_batch_ranges. The batches are the CPU oracle's (tests/test_batch_cpu.py: oracle_batch,
+tests/test_batch_shared_cpu.py: oracle_text_batch), uploaded as they are, so the decoder is judged
+without the encoder; the reference of a range is the slice of its input segment, and every byte
+nobody asked for must keep its 0xA5 prefill."""
+import numpy as np
+import pytest
+
+from tests.test_batch_cpu import SEGMENTS, oracle_batch, pack_offsets
+from tests.test_batch_ranges_cpu import batch_ranges
+from tests.test_batch_shared_cpu import oracle_text_batch, text_table
+
+pytestmark = pytest.mark.gpu
+
+FILL = 0xA5
+DC_E_ARG, DC_E_CAPACITY, DC_E_STREAM = -1, -6, -7
+CASES = [(2, 64), (2, 16), (2, 1024), (3, 64), (17, 64)]
+MODES = ("own", "shared")
+A, B, STORED = 10, 15, 17   # enwik 4097 and enwik 65536 (coded in both modes), cycle 65536 (stored in both)
+
+
+@pytest.fixture(scope="module")
+def torch_cuda():
+    import torch
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    return torch
+
+
+@pytest.fixture(scope="module")
+def codec(torch_cuda):
+    from data_compression_amd.device import Codec
+    return Codec(0)
+
+
+def _dev(torch, a):
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+_uploaded = {}
+
+
+def _enc(torch, codec, mode, n_ary=2, S=64):
+    """The oracle's batch of SEGMENTS on the device, as the dict encode_batch returns (uploaded once
+    per case: the tests clone what they change). status is prefilled with -99: a range call must
+    leave it alone."""
+    key = (mode, n_ary, S)
+    if key not in _uploaded:
+        exp = oracle_batch(SEGMENTS, n_ary, S) if mode == "own" else oracle_text_batch(n_ary, S)
+        x, off = pack_offsets(SEGMENTS)
+        enc = {"count": len(SEGMENTS), "n_ary": n_ary, "S": S, "offsets": _dev(torch, off), "total": x.size,
+               "lens": _dev(torch, exp["lens"]) if mode == "own" else None,
+               "mode": _dev(torch, exp["mode"]), "bits": _dev(torch, exp["bits"].astype(np.int32)),
+               "pay_off": _dev(torch, exp["pay_off"]), "payload": _dev(torch, exp["payload"]),
+               "sync_off": _dev(torch, exp["sync_off"]), "sync_len": _dev(torch, exp["sync_len"].view(np.int16)),
+               "status": torch.full((len(SEGMENTS),), -99, dtype=torch.int32, device="cuda"),
+               "payload_cap": exp["payload"].size, "sync_cap": exp["sync_len"].size}
+        assert enc["payload"].data_ptr() % 16 == 0
+        if mode == "shared":
+            enc["table"] = codec.table_lengths(_dev(torch, text_table(n_ary)), n_ary)
+        _uploaded[key] = enc
+    return _uploaded[key]
+
+
+def _gapped(counts, lead=3, gap=5):
+    """Odd, gapped output starts; returns (starts, capacity)."""
+    at, starts = lead, []
+    for c in counts:
+        starts.append(at)
+        at += int(c) + gap + (at + int(c) + gap + 1) % 2   # keeps every start odd
+    return np.array(starts, np.int64), at + 31
+
+
+def _run(torch, codec, enc, rows, offs=None, cap=None, first=None):
+    """ONE decode_batch_ranges of all rows into a 0xA5 buffer: (bytes, rstatus, offsets), host side."""
+    rows = np.asarray(rows, np.int64).reshape(-1, 3)
+    if offs is None:
+        offs, full = _gapped(rows[:, 2])
+        cap = full if cap is None else cap
+    out = torch.full((cap,), FILL, dtype=torch.uint8, device="cuda")
+    first = _dev(torch, rows[:, 1]) if first is None else first
+    got, _, st = codec.decode_batch_ranges(enc, _dev(torch, rows[:, 0]), first, _dev(torch, rows[:, 2]), out=out,
+                                           out_off=_dev(torch, offs))
+    assert got is out and st.dtype == torch.int32 and st.numel() == len(rows)
+    assert (enc["status"] == -99).all(), "the batch's d_status was written"
+    return out.cpu().numpy(), st.cpu().numpy(), offs
+
+
+def _check(codec, h, st, rows, offs, tag, bad=None):
+    """Every range not in `bad` (index -> expected status) is the slice of its segment; every other
+    byte is untouched; batch_status() is the lowest failing range's status."""
+    bad = bad or {}
+    asked = np.zeros(h.size, bool)
+    for r, ((i, f, c), o) in enumerate(zip(np.asarray(rows).reshape(-1, 3).tolist(), offs)):
+        if r in bad:
+            assert st[r] == bad[r], tag + (r, (i, f, c), "status", int(st[r]))
+            continue
+        assert st[r] == 0, tag + (r, (i, f, c), int(st[r]))
+        assert np.array_equal(h[o: o + c], SEGMENTS[i][f: f + c]), tag + (r, (i, f, c), "decoded bytes")
+        asked[o: o + c] = True
+    assert (h[~asked] == FILL).all(), tag + ("bytes outside the good ranges written",)
+    assert codec.batch_status() == (bad[min(bad)] if bad else 0), tag + ("batch_status",)
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("n_ary,S", CASES)
+def test_the_range_list_in_one_call(torch_cuda, codec, mode, n_ary, S):
+    enc = _enc(torch_cuda, codec, mode, n_ary, S)
+    if (n_ary, S) == (2, 64):
+        m = enc["mode"].cpu().numpy()
+        assert set(m.tolist()) == {0, 1} and m[A] == 1 and m[B] == 1 and m[STORED] == 0
+    rows = batch_ranges(SEGMENTS, S)
+    h, st, offs = _run(torch_cuda, codec, enc, rows)
+    assert (offs % 2 == 1).all()
+    _check(codec, h, st, rows, offs, (mode, n_ary, S))
+
+
+@pytest.mark.parametrize("mode", MODES)
+def test_order_does_not_matter(torch_cuda, codec, mode):
+    """The same list reversed and shuffled, every range at its own output offset: the same bytes."""
+    enc = _enc(torch_cuda, codec, mode)
+    rows = batch_ranges(SEGMENTS, 64)
+    offs, cap = _gapped(rows[:, 2])
+    h0, st0, _ = _run(torch_cuda, codec, enc, rows, offs, cap)
+    _check(codec, h0, st0, rows, offs, (mode, "in order"))
+    for name, perm in (("reversed", np.arange(len(rows))[::-1]), ("shuffled", np.random.default_rng(3).permutation(len(rows)))):
+        h, st, _ = _run(torch_cuda, codec, enc, rows[perm], offs[perm], cap)
+        assert (st == 0).all() and codec.batch_status() == 0, (mode, name)
+        assert np.array_equal(h, h0), (mode, name)
+
+
+@pytest.mark.parametrize("grid", (0, 1))
+@pytest.mark.parametrize("middle", (B, STORED))
+def test_own_tables_are_reused_and_rebuilt(torch_cuda, codec, grid, middle):
+    """Segments A, A, B, A: on a grid of one workgroup the second range reuses A's table, the third
+    rebuilds (or, for a stored segment, needs none), the fourth rebuilds A's."""
+    enc = _enc(torch_cuda, codec, "own")
+    rows = [(A, 10, 300), (A, 1000, 300), (middle, 10, 300), (A, 2000, 2097)]
+    codec.set_option("batch_grid", grid)
+    try:
+        h, st, offs = _run(torch_cuda, codec, enc, rows)
+    finally:
+        codec.set_option("batch_grid", 0)
+    _check(codec, h, st, rows, offs, ("A A B A", grid, middle))
+
+
+@pytest.mark.parametrize("mode", MODES)
+def test_failures_are_local(torch_cuda, codec, mode):
+    torch = torch_cuda
+    enc = _enc(torch, codec, mode)
+    rows = batch_ranges(SEGMENTS, 64, seed=11, nrandom=24)[-24:].copy()
+    n_a = SEGMENTS[A].size
+    bad = {2: DC_E_CAPACITY, 5: DC_E_ARG, 9: DC_E_ARG, 13: DC_E_ARG}
+    rows[2] = (A, 7, 20)               # its output passes out_cap by one byte
+    rows[5] = (len(SEGMENTS), 0, 1)    # seg = count
+    rows[9] = (A, n_a - 9, 10)         # first + count = len + 1
+    rows[13] = (A, -1, 2)              # first = 2^64 - 1: first + count wraps to 1
+    offs, cap = _gapped(rows[:, 2])
+    offs[2] = cap - 20 + 1
+    first = _dev(torch, rows[:, 1])
+    assert int(first[13]) == -1        # the kernels read it as u64
+    h, st, _ = _run(torch, codec, enc, rows, offs, cap, first=first)
+    _check(codec, h, st, rows, offs, (mode, "failures"), bad=bad)
+
+
+@pytest.mark.parametrize("mode", MODES)
+def test_corruption_is_seen_by_the_ranges_that_touch_it(torch_cuda, codec, mode):
+    torch = torch_cuda
+    good = _enc(torch, codec, mode)
+    S, c = 64, 3
+    assert int(good["mode"][A]) == 1 and SEGMENTS[A].size >= 8 * S
+    n_a = SEGMENTS[A].size
+    rows = [(A, c * S, 1), (A, (c + 1) * S + 5, 10), (A, c * S - 1, 2), (A, (c + 2) * S - 1, 2), (A, 0, n_a),   # touch c or c + 1
+            (A, 0, c * S), (A, 100, 50), (A, (c + 2) * S, 100), (A, (c + 2) * S, n_a - (c + 2) * S), (A, n_a - 1, 1),
+            (A, 0, 0), (B, 0, SEGMENTS[B].size), (B, c * S, 2 * S), (STORED, c * S - 1, 2 * S + 2)]
+    enc = dict(good, sync_len=good["sync_len"].clone())
+    at = int(good["sync_off"][A]) + c
+    enc["sync_len"][at] += 1       # the sum is kept: only the per-chunk exactness check can see it
+    enc["sync_len"][at + 1] -= 1
+    h, st, offs = _run(torch, codec, enc, rows)
+    _check(codec, h, st, rows, offs, (mode, "sync_len"), bad={r: DC_E_STREAM for r in range(5)})
+    # a mode byte of 2: that segment's ranges only (one that asks for nothing reads no record)
+    enc = dict(good, mode=good["mode"].clone())
+    enc["mode"][A] = 2
+    h, st, offs = _run(torch, codec, enc, rows)
+    _check(codec, h, st, rows, offs, (mode, "mode"), bad={r: DC_E_STREAM for r in range(10)})
+
+
+def test_a_table_of_another_arity_is_refused(torch_cuda, codec):
+    """The batch says n = 3, the table is n = 2: DC_E_ARG for every range, nothing written. (The
+    table is test 6 of the order in dc_gpu.h: a range that asks for nothing is DC_OK before it.)"""
+    enc = dict(_enc(torch_cuda, codec, "shared"), n_ary=3)
+    rows = batch_ranges(SEGMENTS, 64, nrandom=40)
+    rows = rows[rows[:, 2] > 0]
+    h, st, offs = _run(torch_cuda, codec, enc, rows)
+    assert len(rows) > 100 and (st == DC_E_ARG).all()
+    assert (h == FILL).all() and codec.batch_status() == DC_E_ARG
+    h, st, offs = _run(torch_cuda, codec, enc, [(A, 0, 0), (A, 5, 5)])
+    assert st.tolist() == [0, DC_E_ARG] and (h == FILL).all() and codec.batch_status() == DC_E_ARG
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("grid", (0, 1))
+@pytest.mark.parametrize("nranges", (1, 3, 4, 5, 1025))
+def test_counts_and_grids(torch_cuda, codec, mode, grid, nranges):
+    enc = _enc(torch_cuda, codec, mode)
+    rows = batch_ranges(SEGMENTS, 64, seed=100 + nranges, nrandom=nranges)[-nranges:]
+    codec.set_option("batch_grid", grid)
+    try:
+        h, st, offs = _run(torch_cuda, codec, enc, rows)
+    finally:
+        codec.set_option("batch_grid", 0)
+    _check(codec, h, st, rows, offs, (mode, grid, nranges))
+
+
+@pytest.mark.parametrize("mode", MODES)
+def test_launches_do_not_depend_on_count(torch_cuda, codec, mode):
+    enc = _enc(torch_cuda, codec, mode)
+    stages = {}
+    for nranges in (0, 1, 1025):
+        rows = batch_ranges(SEGMENTS, 64, seed=5, nrandom=nranges)[-nranges:] if nranges else np.zeros((0, 3), np.int64)
+        codec.timing(True)
+        _run(torch_cuda, codec, enc, rows)
+        stages[nranges] = [n for n, _ in codec.timings()]
+        codec.timing(False)
+    assert stages[0] == []                                  # no launch
+    assert stages[1] == stages[1025] and len(stages[1]) == 1
+    assert stages[1] == ["hb_decode_ranges" if mode == "own" else "hbs_decode_ranges"]
+
+
+@pytest.mark.parametrize("mode", MODES)
+def test_python_sequences_and_the_packed_default(torch_cuda, codec, mode):
+    """Sequences for seg / first / count, no out and no out_off: the ranges back to back."""
+    enc = _enc(torch_cuda, codec, mode)
+    rows = [(A, 5, 300), (STORED, 60000, 5536), (B, 4000, 97), (A, 0, 0), (1, 0, 1)]
+    out, off, st = codec.decode_batch_ranges(enc, [r[0] for r in rows], [r[1] for r in rows], [r[2] for r in rows])
+    assert st.cpu().tolist() == [0] * len(rows) and codec.batch_status() == 0
+    assert off.cpu().tolist() == [0, 300, 5836, 5933, 5933] and out.numel() == 5934
+    assert np.array_equal(out.cpu().numpy(), np.concatenate([SEGMENTS[i][f: f + c] for i, f, c in rows]))

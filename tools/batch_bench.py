@@ -12,10 +12,22 @@ of bench.py (synth.device_text, seed 0xC2, n = 2, S = 64), one process:
           index + 5 B per segment + the table's lengths once) beside the own-table size; then at
           4 KiB the own-table call against the shared call, alternating in this process; asserts
           that the shared encode and decode are each faster and that the shared form is smaller
+  ranges  (only on request) random 256-byte ranges of the blocks under the shared table, one
+          decode_batch_ranges call against all a caller could do before: the whole-segment scatter
+          decode of exactly the distinct segments the ranges touch (the others are skipped the
+          one way the API has, an output range that ends before it starts: nothing of them is read,
+          but each is visited and takes the failure path, a status store and an atomicMin on the
+          call's first-failure word, which at 4 KiB blocks and few ranges is most of the time), then
+          the wanted bytes sliced out by a precomputed index. The two sides alternate, the median of
+          `--rounds` rounds of HIP-event windows of at least 20 ms; asserts that at 4096 ranges of
+          the 64 KiB blocks the range call is faster. Then own tables at 65536 ranges, sorted by
+          segment and not, and Codec.decode_ranges on the single stream of the same text.
 Every result is checked against the input before it is timed. One JSON line per result.
     timeout 900 python tools/batch_bench.py [--size BYTES] [--steps K] [--rounds R] [--only blocks,loop,shared]
+    timeout 900 python tools/batch_bench.py --only ranges
 """
 import argparse
+import ctypes
 import json
 import os
 import statistics
@@ -211,3 +223,116 @@ if "shared" in a.only:
             assert size["shared"] < size["own"], "the shared-table form is not smaller than the own-table form"
         del encs, bufs
     del out
+
+if "ranges" in a.only:
+    RB = 256   # bytes per range
+    tab = c.batch_table(x, n_ary=2)
+    gen = torch.Generator(device=dev)
+    lane = torch.arange(RB, dtype=torch.int64, device=dev)
+
+    def timed_pair(fns):
+        """{name: median ms}, {name: (min, max)}: the sides alternating, windows of >= 20 ms."""
+        steps = {}
+        for k, fn in fns.items():
+            fn()
+            torch.cuda.synchronize()
+            steps[k] = max(a.steps, min(400, int(20.0 / max(ev_ms(fn, 1), 1e-3)) + 1))
+        t = {k: [] for k in fns}
+        for _ in range(a.rounds):
+            for k, fn in fns.items():
+                t[k].append(ev_ms(fn, steps[k]))
+        return ({k: statistics.median(v) for k, v in t.items()}, {k: (round(min(v), 4), round(max(v), 4)) for k, v in t.items()},
+                steps)
+
+    def draw(count, block, nr, seed):
+        gen.manual_seed(seed)
+        seg = torch.randint(0, count, (nr,), generator=gen, device=dev, dtype=torch.int64)
+        first = torch.randint(0, block - RB + 1, (nr,), generator=gen, device=dev, dtype=torch.int64)
+        return seg, first
+
+    def range_row(enc, block, nr, seg, first, table, order, baseline):
+        count = enc["count"]
+        cnt = torch.full((nr,), RB, dtype=torch.int64, device=dev)
+        ooff = torch.arange(nr, dtype=torch.int64, device=dev) * RB
+        want = torch.take(x, ((seg * block + first)[:, None] + lane).reshape(-1))
+        out_r = torch.zeros(nr * RB, dtype=torch.uint8, device=dev)
+
+        def ranges():
+            c.decode_batch_ranges(enc, seg, first, cnt, out=out_r, out_off=ooff)
+
+        ranges()
+        assert c.batch_status() == 0 and torch.equal(out_r, want), "the range call differs from the input"
+        fns = {"ranges": ranges}
+        row = {"what": "ranges", "table": table, "order": order, "block": block, "count": count, "nranges": nr,
+               "range_bytes": RB, "delivered_bytes": nr * RB}
+        if baseline:
+            touched = torch.unique(seg)
+            nd = touched.numel()
+            rank = torch.searchsorted(touched, seg)
+            beg = torch.ones(count, dtype=torch.int64, device=dev)     # untouched: [1, 0), refused unread
+            end = torch.zeros(count, dtype=torch.int64, device=dev)
+            beg[touched] = torch.arange(nd, dtype=torch.int64, device=dev) * block
+            end[touched] = beg[touched] + (enc["offsets"][1:] - enc["offsets"][:-1])[touched]
+            buf = torch.zeros(nd * block, dtype=torch.uint8, device=dev)
+            pick = ((rank * block + first)[:, None] + lane).reshape(-1)
+            out_b = torch.zeros(nr * RB, dtype=torch.uint8, device=dev)
+            hb = c._hbatch(enc, enc["payload_cap"], enc["sync_cap"])
+            args = (c.ctx, ctypes.byref(hb)) + ((tab.data_ptr(),) if "table" in enc else ()) + \
+                (buf.data_ptr(), beg.data_ptr(), end.data_ptr(), buf.numel())
+            fn = c.L.dc_huff_decode_batch_shared_scatter if "table" in enc else c.L.dc_huff_decode_batch_scatter
+
+            def whole():
+                assert fn(*args) == 0
+                torch.take(buf, pick, out=out_b)
+
+            whole()
+            st = enc["status"][touched]
+            assert bool((st == 0).all()) and torch.equal(out_b, want), "the baseline differs from the input"
+            fns["whole_segments"] = whole
+            row.update(distinct_segments=nd, baseline_decoded_bytes=int((end - beg)[touched].sum()),
+                       density_pct=round(100.0 * nr * RB / (nd * block), 2))
+        med, mm, steps = timed_pair(fns)
+        row.update(ranges_ms=round(med["ranges"], 4), ranges_delivered_GBps=round(nr * RB / med["ranges"] / 1e6, 2),
+                   ranges_min_max_ms=mm["ranges"], steps=steps)
+        if baseline:
+            row.update(whole_ms=round(med["whole_segments"], 4), whole_delivered_GBps=round(nr * RB / med["whole_segments"] / 1e6, 2),
+                       whole_min_max_ms=mm["whole_segments"], speedup=round(med["whole_segments"] / med["ranges"], 2))
+        emit(**row)
+        return row
+
+    rows = {}
+    for block in (65536, 4096):
+        count = (n + block - 1) // block
+        enc = c.encode_blocks(x, block=block, n_ary=2, sync_syms=S, table=tab)
+        assert c.batch_status() == 0
+        for lg in (12, 16, 18, 19, 20) + ((22,) if block == 4096 else ()):   # (2^22 x 256 B of 4 KiB blocks: every byte once on average)
+            seg, first = draw(count, block, 1 << lg, 0xC2 + lg)
+            rows[(block, lg)] = range_row(enc, block, 1 << lg, seg, first, "shared", "random", True)
+        del enc
+        enc = c.encode_blocks(x, block=block, n_ary=2, sync_syms=S)
+        assert c.batch_status() == 0
+        seg, first = draw(count, block, 1 << 16, 0xC2 + 16)
+        range_row(enc, block, 1 << 16, seg, first, "own", "random", False)
+        srt = torch.argsort(seg)
+        range_row(enc, block, 1 << 16, seg[srt].contiguous(), first[srt].contiguous(), "own", "sorted by segment", False)
+        del enc
+    # for context: the same 65536 ranges of the single-table stream of the whole text (Codec.decode_ranges)
+    single = c.encode(x, n_ary=2, sync_syms=S)
+    nr = 1 << 16
+    seg, first = draw(n // 65536, 65536, nr, 0xC2 + 16)
+    pos = seg * 65536 + first
+    cnt = torch.full((nr,), RB, dtype=torch.int64, device=dev)
+    ooff = torch.arange(nr, dtype=torch.int64, device=dev) * RB
+    out_s = torch.zeros(nr * RB, dtype=torch.uint8, device=dev)
+    want = torch.take(x, (pos[:, None] + lane).reshape(-1))
+
+    def single_ranges():
+        c.decode_ranges(single, pos, cnt, out=out_s, out_off=ooff)
+
+    single_ranges()
+    assert c.decode_status() == 0 and torch.equal(out_s, want)
+    med, mm, steps = timed_pair({"single": single_ranges})
+    emit(what="ranges_single_stream", nranges=nr, range_bytes=RB, ms=round(med["single"], 4),
+         delivered_GBps=round(nr * RB / med["single"] / 1e6, 2), min_max_ms=mm["single"], steps=steps)
+    r = rows[(65536, 12)]
+    assert r["ranges_ms"] < r["whole_ms"], "4096 ranges of 256 B from 64 KiB blocks are not faster than decoding their segments"
