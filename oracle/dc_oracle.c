@@ -507,6 +507,8 @@ uint64_t orc_small_decompress(const uint8_t *in, uint64_t m, uint8_t *out)
         memcpy(out, in + 1, (size_t)(m - 1));
         return m - 1;
     }
-    memcpy(out, in, (size_t)m);
-    return m;
+    /* any other type byte: "invalid compressed data", the output stays empty
+     * (small_compression.c:495-503). The nybble decoder copies such a stream
+     * (nybble_compression.c:806); this one does not. */
+    return 0;
 }
