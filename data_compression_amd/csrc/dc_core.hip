@@ -18,6 +18,7 @@
 
 #include "dc_gpu.h"
 #include "dc_batch_bound.h"
+#include "dc_nyb_batch_bound.h"
 #include "dc_batch_range.h"
 
 #define DC_VERSION "dc-mi355x 0.1 (gfx950)"
@@ -6270,6 +6271,7 @@ __global__ __launch_bounds__(256) void k_copy_probe(const uint4 *__restrict__ sr
 #include "dc_batch_kernels.inc"
 #include "dc_batch_shared_kernels.inc"
 #include "dc_batch_range_kernels.inc"
+#include "dc_nyb_batch_kernels.inc"
 
 #ifdef DC_AB_KERNELS
 #include "dc_ab_kernels.inc"
@@ -7889,6 +7891,39 @@ int dc_nyb_decompress_batch(dc_ctx *c, const uint8_t *d_in, const uint64_t *d_in
     HIPCHK(hipMemcpyAsync(c->h_pinned, err, 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     return c->h_pinned[0] ? DC_E_STREAM : DC_OK;
+}
+
+// ---- nybble batch v1 (dc_nyb_batch_kernels.inc) ----------------------------------------
+uint64_t dc_nyb_batch_bound(uint64_t total_bytes, uint64_t count) { return dc_nyb_batch_bound_calc(total_bytes, count); }
+
+int dc_nyb_compress_batch(dc_ctx *c, const uint8_t *d_in, const uint64_t *d_in_off, uint64_t count, int modify,
+                          uint8_t *d_out, uint64_t out_cap, uint64_t *d_out_off, int32_t *d_status)
+{
+    if (!c) return DC_E_ARG;
+    if (count == 0) return DC_OK;
+    if (count > DC_RANGES_MAX || !d_in || !d_in_off || !d_out || !d_out_off || !d_status) return DC_E_ARG;
+    unsigned long long *first;
+    if (const int r = hbatch_begin(c, count, &first)) return r;
+    uint64_t *const lens = c->d_hb + 2;
+    const uint64_t grid = (count + 63) / 64;
+    LAUNCH(c, "nyb_batch_enc_len", k_nyb_batch_enc_len, grid, 64, d_in, d_in_off, count, modify ? 1 : 0, lens);
+    LAUNCH(c, "nyb_batch_enc_scan", k_scan_u64, 1, 1024, (const uint64_t *)lens, count, d_out_off);
+    LAUNCH(c, "nyb_batch_enc", k_nyb_batch_enc, grid, 64, d_in, d_in_off, (const uint64_t *)d_out_off, count,
+           modify ? 1 : 0, d_out, out_cap, d_status, first);
+    return DC_OK;
+}
+
+int dc_nyb_decompress_batch_async(dc_ctx *c, const uint8_t *d_in, const uint64_t *d_in_off, uint64_t count, int modify,
+                                  uint8_t *d_out, const uint64_t *d_out_off, uint64_t out_cap, int32_t *d_status)
+{
+    if (!c) return DC_E_ARG;
+    if (count == 0) return DC_OK;
+    if (count > DC_RANGES_MAX || !d_in || !d_in_off || !d_out || !d_out_off || !d_status) return DC_E_ARG;
+    unsigned long long *first;
+    if (const int r = hbatch_begin(c, count, &first)) return r;
+    LAUNCH(c, "nyb_batch_dec_async", k_nyb_batch_dec_async, (count + 63) / 64, 64, d_in, d_in_off, d_out_off, count,
+           modify ? 1 : 0, d_out, out_cap, d_status, first);
+    return DC_OK;
 }
 
 // ---- nybble shard bodies (dist.ShardedNybble) ---------------------------

@@ -557,7 +557,9 @@ int dc_nyb_decompress(dc_ctx *ctx, const uint8_t *d_in, uint64_t m, int modify, 
  * alone. Layout: u32 'DCNK', u32 version 1, u32 modify, u32 K, u64 n, u64 nchunks,
  * u64 off[nchunks+1] (relative to the payload), payload. K >= 16; d_out / d_in 8-B aligned.
  * Decode returns DC_E_STREAM when a chunk does not decode to exactly its length (a corrupt
- * container, or input bytes >= 0x80, which the reference codec does not round-trip). */
+ * container, or input bytes >= 0x80, which the reference codec does not round-trip). Input
+ * byte 0 is outside the reference's domain (NUL-terminated strings) and not exact here: the
+ * one-lane-per-chunk kernels pad their lists with zero bytes (see "nybble batch v1" below). */
 uint64_t dc_nyb_chunked_bound(uint64_t n, uint32_t K);
 int dc_nyb_compress_chunked(dc_ctx *ctx, const uint8_t *d_in, uint64_t n, int modify, uint32_t K, uint8_t *d_out,
                             uint64_t out_cap, uint64_t *h_out_len);
@@ -575,6 +577,60 @@ int dc_nyb_decompress_chunked(dc_ctx *ctx, const uint8_t *d_in, uint64_t m, uint
  * offset range that ends before it starts. Synchronising. */
 int dc_nyb_decompress_batch(dc_ctx *ctx, const uint8_t *d_in, const uint64_t *d_in_off, uint64_t count, int modify,
                             uint8_t *d_out, uint64_t out_cap, uint64_t *d_out_off, uint64_t *h_total);
+/* ---- nybble batch v1: many buffers of their own lengths, one call each way -------------------
+ * The format is nothing but the reference's own streams back to back plus their offsets: no
+ * header, no container. Both calls are asynchronous on the context's stream, make no host read,
+ * and launch the same kernels for any count and any lengths, so a round trip can be enqueued or
+ * captured (the first call at a larger count grows the context's 16 B of scratch per buffer).
+ * count 0 returns DC_OK without a launch; count > DC_RANGES_MAX, a NULL context or (with
+ * count > 0) any NULL pointer returns DC_E_ARG. A bad buffer never stops the others.
+ * d_status[i] (i32, count entries) receives each buffer's outcome, and dc_huff_batch_status
+ * (there is no nybble twin: the context keeps one first-failure slot for every batch call)
+ * reports the lowest failing index of the last such call, synchronising.
+ *
+ * dc_nyb_batch_bound = total_bytes + count: a buffer of len >= 1 bytes codes to at most len + 1
+ * bytes (the LITERAL form), an empty one to the single byte ' '. Exact, and pure host arithmetic
+ * (csrc/dc_nyb_batch_bound.h).
+ *
+ * dc_nyb_compress_batch: buffer i = d_in[d_in_off[i] .. d_in_off[i+1]) (device u64, count + 1
+ * entries; any alignment, any length, 0 too). Stream i is exactly what dc_nyb_compress writes for
+ * that buffer alone (type byte 0xAF, the raw first byte, nybbles; ' ' and the raw bytes when the
+ * nybble form is not shorter; ' ' alone for length 0), with the static or the adaptive (modify)
+ * lists. The streams lie back to back in d_out: the call writes d_out_off[0] = 0 and
+ * d_out_off[i+1] = d_out_off[i] + (length of stream i), count + 1 entries, always the true
+ * lengths, so d_out_off[count] is the capacity the batch needs even when out_cap was too small.
+ *   DC_E_ARG       the buffer's offsets decrease: it takes 0 output bytes, and nothing of it is
+ *                  read or written
+ *   DC_E_CAPACITY  d_out_off[i+1] > out_cap: nothing of it is written
+ * Nothing is ever written at or past d_out + out_cap, and no byte of d_out that belongs to no
+ * stream is written.
+ * Byte domain: for buffers of bytes 1..255 the streams are the reference's. Byte 0 is outside the
+ * reference's domain (its API takes NUL-terminated strings), and the one-lane-per-stream kernels
+ * keep their lists padded with zero bytes, which is not exact for a zero input byte: such input
+ * stays inside every bound above and gives the same output on every run, but its streams need not
+ * be the reference's nor decode to the input. The DCNK container has the same limit.
+ * Cost: a length walk, a scan and an encode straight to the final place (the scratch-slot form of
+ * DCNK would need the input total on the host, and slots that stay disjoint beside a decreasing
+ * offset pair), so each buffer is walked twice. One lane codes one buffer, 64 buffers a wave, and a
+ * wave runs for as long as its longest buffer: batches of very unequal lengths are best sorted by
+ * length (tools/nyb_batch_bench.py records the difference). There is no maximum buffer length.
+ *
+ * dc_nyb_decompress_batch_async: stream i = d_in[d_in_off[i] .. d_in_off[i+1]) is decoded into
+ * d_out[d_out_off[i] .. d_out_off[i+1]), where the CALLER gives d_out_off (count + 1 entries): the
+ * format stores no length, so the length asked for must be the stream's. The type dispatch is
+ * dc_nyb_decompress_batch's (0xAF nybbles, ' ' raw, any other type byte copies the whole stream).
+ * One launch.
+ *   DC_E_ARG       either offset pair decreases: nothing is read or written
+ *   DC_E_CAPACITY  d_out_off[i+1] > out_cap: nothing is written
+ *   DC_E_STREAM    the stream does not decode to exactly the asked length
+ * No byte outside a stream's own asked range is ever written. The contents of a FAILED stream's
+ * own range are unspecified: there is no framing to verify before the walk, and a verify pass
+ * (a second walk of every stream) is not worth its cost here. */
+uint64_t dc_nyb_batch_bound(uint64_t total_bytes, uint64_t count);
+int dc_nyb_compress_batch(dc_ctx *ctx, const uint8_t *d_in, const uint64_t *d_in_off, uint64_t count, int modify,
+                          uint8_t *d_out, uint64_t out_cap, uint64_t *d_out_off, int32_t *d_status);
+int dc_nyb_decompress_batch_async(dc_ctx *ctx, const uint8_t *d_in, const uint64_t *d_in_off, uint64_t count, int modify,
+                                  uint8_t *d_out, const uint64_t *d_out_off, uint64_t out_cap, int32_t *d_status);
 /* Shard bodies (data_compression_amd/dist.py ShardedNybble). A shard buffer is
  * d_in[0 .. len): d_in[0] is the context byte (the stream's first byte on the first shard, the
  * previous shard's last byte after it) and the shard's elements are bytes 1 .. len-1, as in

@@ -1,0 +1,317 @@
+"""The batched nybble codec on the device: dc_nyb_compress_batch (k_nyb_batch_enc_len, k_scan_u64,
+k_nyb_batch_enc) and dc_nyb_decompress_batch_async (k_nyb_batch_dec_async) through
+Codec.nyb_compress_batch / nyb_compress_blocks / nyb_decompress_batch_into. The reference is the CPU
+oracle's stream of every buffer alone (tests/test_nyb_batch_cpu.py: oracle_streams) for the encode
+and orc.nybble_decompress for the decode; every byte nobody asked for must keep its 0xA5 prefill.
+
+One buffer of STREAM_INPUTS (I_HIGH) holds bytes >= 0x80, which the reference codec does not
+round-trip (a raw byte with bit 7 set reads back as a hit nybble): its decode is checked against
+orc.nybble_decompress of its stream, like every other, and not against the input."""
+import numpy as np
+import pytest
+
+from oracle import oracle as orc
+from tests.test_nyb_batch_cpu import I_HIGH, I_RANDOM_100, STREAM_INPUTS, oracle_streams, pack_offsets
+
+pytestmark = pytest.mark.gpu
+
+FILL = 0xA5
+DC_E_ARG, DC_E_CAPACITY, DC_E_STREAM = -1, -6, -7
+MODES = (False, True)
+
+
+@pytest.fixture(scope="module")
+def torch_cuda():
+    import torch
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    return torch
+
+
+@pytest.fixture(scope="module")
+def codec(torch_cuda):
+    from data_compression_amd.device import Codec
+    return Codec(0)
+
+
+def _dev(torch, a):
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def _cum(streams):
+    off = np.zeros(len(streams) + 1, np.int64)
+    off[1:] = np.cumsum([len(s) for s in streams])
+    return off
+
+
+def _encode(torch, codec, x, off, modify, out_cap=None):
+    """nyb_compress_batch into a 0xA5-filled buffer of bound + 48 bytes: host (out, out_off, status)."""
+    count = len(off) - 1
+    out = torch.full((codec.nyb_batch_bound(x.size, count) + 48,), FILL, dtype=torch.uint8, device="cuda")
+    o, oo, st = codec.nyb_compress_batch(_dev(torch, x), _dev(torch, off), modify, out=out, out_cap=out_cap)
+    assert o is out
+    return out.cpu().numpy(), oo.cpu().numpy(), st.cpu().numpy()
+
+
+def _check_streams(h, oo, st, want, tag, bad=None):
+    """Every stream not in `bad` (index -> status) is the oracle's at its place; a bad one takes
+    the bytes want[i] says (b"" for DC_E_ARG) and writes none; all else keeps the prefill."""
+    bad = bad or {}
+    exp_off = _cum(want)
+    assert np.array_equal(oo, exp_off), tag + ("out_off",)
+    written = np.zeros(h.size, bool)
+    for i, s in enumerate(want):
+        if i in bad:
+            assert st[i] == bad[i], tag + (i, "status", int(st[i]))
+            continue
+        assert st[i] == 0, tag + (i, int(st[i]))
+        assert h[exp_off[i]: exp_off[i + 1]].tobytes() == s, tag + (i, "stream")
+        written[exp_off[i]: exp_off[i + 1]] = True
+    assert (h[~written] == FILL).all(), tag + ("bytes of no good stream written",)
+
+
+@pytest.fixture(scope="module")
+def encoded(torch_cuda, codec):
+    """STREAM_INPUTS through the batch encode once per mode: host (out, out_off, status), the
+    batch status right after the call, and the packed input. Do not modify."""
+    x, off = pack_offsets(STREAM_INPUTS)
+    res = {}
+    for modify in MODES:
+        h = _encode(torch_cuda, codec, x, off, modify)
+        res[modify] = h + (codec.batch_status(),)
+    return res, x, off
+
+
+@pytest.mark.parametrize("modify", MODES)
+def test_encode_is_the_oracle_stream_of_every_buffer(encoded, modify):
+    res, x, off = encoded
+    h, oo, st, bstat = res[modify]
+    want = oracle_streams(STREAM_INPUTS, modify)
+    assert {s[0] for s in want} == {0xAF, 0x20}   # both forms are in the batch
+    assert bstat == 0 and (st == 0).all()
+    _check_streams(h, oo, st, want, (modify,))
+    assert (h[oo[-1]:] == FILL).all() and h.size - oo[-1] >= 48
+
+
+@pytest.mark.parametrize("modify", MODES)
+def test_same_streams_as_the_single_call(torch_cuda, codec, encoded, modify):
+    res, x, off = encoded
+    h, oo, _, _ = res[modify]
+    sample = [1, 2, 5, 6, 9, 10, 33, 59, 60, 61, 62, 66, 69, I_RANDOM_100, I_RANDOM_100 + 1, I_HIGH, 100, 200, 300, 372]
+    for i in sample:
+        one = codec.nyb_compress(_dev(torch_cuda, STREAM_INPUTS[i]), modify).cpu().numpy()
+        assert np.array_equal(one, h[oo[i]: oo[i + 1]]), (modify, i)
+
+
+@pytest.fixture(scope="module")
+def wave_text():
+    """129 buffers of 33 bytes from offset 5 of one text: the starts take every residue mod 16
+    (33 = 2 x 16 + 1), 15 in 16 of them no multiple of 16, every buffer sharing its first and last
+    granule with its neighbours. (text, oracle streams per mode)."""
+    from data_compression_amd import synth
+    text = synth.english_like(5 + 33 * 129 + 11, seed=33)
+    bufs = [text[5 + 33 * i: 5 + 33 * (i + 1)] for i in range(129)]
+    return text, {m: oracle_streams(bufs, m) for m in MODES}
+
+
+@pytest.mark.parametrize("modify", MODES)
+@pytest.mark.parametrize("count", (1, 63, 64, 65, 129))
+def test_wave_edges(torch_cuda, codec, wave_text, count, modify):
+    text, want = wave_text
+    off = 5 + 33 * np.arange(count + 1, dtype=np.int64)
+    h, oo, st = _encode(torch_cuda, codec, text, off, modify)
+    assert codec.batch_status() == 0
+    _check_streams(h, oo, st, want[modify][:count], (count, modify))
+
+
+@pytest.mark.parametrize("modify", MODES)
+@pytest.mark.parametrize("k", (20, 200, 372))   # the first, a middle and the last wave of 6
+def test_capacity_falls_inside_a_stream(torch_cuda, codec, k, modify):
+    x, off = pack_offsets(STREAM_INPUTS)
+    want = oracle_streams(STREAM_INPUTS, modify)
+    exp_off = _cum(want)
+    assert len(want[k]) >= 2 and (len(STREAM_INPUTS) + 63) // 64 == 6
+    cap = int(exp_off[k]) + len(want[k]) // 2
+    h, oo, st = _encode(torch_cuda, codec, x, off, modify, out_cap=cap)
+    assert codec.batch_status() == DC_E_CAPACITY
+    _check_streams(h, oo, st, want, (k, modify), bad={i: DC_E_CAPACITY for i in range(k, len(want))})
+    assert (h[exp_off[k]:] == FILL).all()
+
+
+@pytest.mark.parametrize("modify", MODES)
+def test_a_decreasing_offset_pair_fails_alone(torch_cuda, codec, modify):
+    """off[j + 1] set 7 below off[j]: buffer j ends before it starts (DC_E_ARG, 0 bytes), and
+    buffer j + 1 starts inside buffer j - 1; every good buffer is coded as what its offsets say."""
+    x, off = pack_offsets(STREAM_INPUTS)
+    j = 150
+    off = off.copy()
+    off[j + 1] = off[j] - 7
+    want = list(oracle_streams(STREAM_INPUTS, modify))
+    want[j] = b""
+    want[j + 1] = orc.nybble_compress(x[off[j + 1]: off[j + 2]].tobytes(), modify)
+    h, oo, st = _encode(torch_cuda, codec, x, off, modify)
+    assert codec.batch_status() == DC_E_ARG
+    _check_streams(h, oo, st, want, (modify,), bad={j: DC_E_ARG})
+
+
+def test_no_buffers_touches_nothing(torch_cuda, codec):
+    h, oo, st = _encode(torch_cuda, codec, np.zeros(0, np.uint8), np.zeros(1, np.int64), True)
+    assert (h == FILL).all() and st.size == 0 and oo.tolist() == [0]
+
+
+def _decode_gapped(torch, codec, streams, lens, modify, tag, bad=None):
+    """The streams decoded at gapped output starts (lead 3, gap 5) in ONE call. out_off has count
+    + 1 entries, so a gap is an entry of its own: the streams lie in REVERSE order in the input
+    (a pad byte between them), which makes the input range of every gap entry, [end of stream i,
+    start of stream i + 1), end before it starts: DC_E_ARG, nothing read or written. `lens` are
+    the lengths asked for; streams in `bad` (index -> status) fail, and their own ranges may hold
+    anything. Returns the host output and the (starts, ends) of the streams."""
+    bad = bad or {}
+    n = len(streams)
+    starts = 3 + np.concatenate([[0], np.cumsum(np.array(lens[:-1], np.int64) + 5)]).astype(np.int64)
+    ends = starts + np.array(lens, np.int64)
+    cap = int(ends[-1]) + 5 + 31
+    data = np.full(sum(map(len, streams)) + n, 0x3F, np.uint8)
+    in_off = np.empty(2 * n, np.int64)
+    pos = data.size
+    for i, s in enumerate(streams):
+        pos -= len(s) + 1
+        data[pos: pos + len(s)] = np.frombuffer(s, np.uint8)
+        in_off[2 * i], in_off[2 * i + 1] = pos, pos + len(s)
+    assert (in_off[2::2] < in_off[1:-1:2]).all()   # every gap entry's input range decreases
+    out_off = np.empty(2 * n, np.int64)
+    out_off[0::2], out_off[1::2] = starts, ends
+    out = torch.full((cap,), FILL, dtype=torch.uint8, device="cuda")
+    o, st = codec.nyb_decompress_batch_into(_dev(torch, data), _dev(torch, in_off), modify, _dev(torch, out_off), out=out)
+    assert o is out
+    h, st = o.cpu().numpy(), st.cpu().numpy()
+    assert st.size == 2 * n - 1 and (st[1::2] == DC_E_ARG).all(), tag + ("gap entries",)
+    st = st[0::2]
+    asked = np.zeros(cap, bool)
+    for i in range(n):
+        asked[starts[i]: ends[i]] = True
+        assert st[i] == bad.get(i, 0), tag + (i, "status", int(st[i]))
+    assert (h[~asked] == FILL).all(), tag + ("bytes outside the asked ranges written",)
+    lowest = DC_E_ARG if n > 1 else 0   # entry 1, the first gap ...
+    if 0 in bad:
+        lowest = bad[0]                 # ... unless stream 0 (entry 0) fails
+    assert codec.batch_status() == lowest, tag + ("batch_status",)
+    return h, starts, ends
+
+
+def _high_outcome(modify):
+    """What decoding I_HIGH's stream gives: (decoded bytes, whether that is its 810 bytes long)."""
+    dec = orc.nybble_decompress(oracle_streams(STREAM_INPUTS, modify)[I_HIGH], modify)
+    return dec, len(dec) == STREAM_INPUTS[I_HIGH].size
+
+
+@pytest.mark.parametrize("modify", MODES)
+def test_async_decode_round_trip(torch_cuda, codec, encoded, modify):
+    torch = torch_cuda
+    res, x, off = encoded
+    h, oo, _, _ = res[modify]
+    dec_high, high_fits = _high_outcome(modify)
+    out = torch.full((x.size + 40,), FILL, dtype=torch.uint8, device="cuda")
+    o, st = codec.nyb_decompress_batch_into(_dev(torch, h[: oo[-1]]), _dev(torch, oo), modify, _dev(torch, off), out=out)
+    got, st = o.cpu().numpy(), st.cpu().numpy()
+    for i, b in enumerate(STREAM_INPUTS):
+        if i == I_HIGH and not high_fits:
+            assert st[i] == DC_E_STREAM
+            continue
+        assert st[i] == 0, (modify, i, int(st[i]))
+        want = dec_high if i == I_HIGH else b.tobytes()
+        assert got[off[i]: off[i + 1]].tobytes() == want, (modify, i)
+    assert (got[x.size:] == FILL).all()
+    assert codec.batch_status() == (0 if high_fits else DC_E_STREAM)
+
+
+@pytest.mark.parametrize("modify", MODES)
+def test_async_decode_at_gapped_starts(torch_cuda, codec, modify):
+    streams = oracle_streams(STREAM_INPUTS, modify)
+    lens = [b.size for b in STREAM_INPUTS]
+    dec_high, high_fits = _high_outcome(modify)
+    bad = {} if high_fits else {I_HIGH: DC_E_STREAM}
+    h, starts, ends = _decode_gapped(torch_cuda, codec, streams, lens, modify, (modify,), bad=bad)
+    for i, b in enumerate(STREAM_INPUTS):
+        if i not in bad:
+            assert h[starts[i]: ends[i]].tobytes() == (dec_high if i == I_HIGH else b.tobytes()), (modify, i)
+
+
+@pytest.fixture(scope="module")
+def mixed_streams():
+    """The stream list of test_gpu_parity.py::test_nybble_batch_decode_vs_oracle: every size 1..40,
+    LITERAL streams, other type bytes (copied whole), arbitrary nybble bytes, a lone 0xAF, empty."""
+    from data_compression_amd import synth
+    res = {}
+    for modify in MODES:
+        rng = np.random.default_rng(41)
+        streams = [b""]
+        for n in list(range(1, 41)) + [100, 4095, 4096, 4097, 65_537]:
+            streams.append(orc.nybble_compress(synth.english_like(n, seed=n).tobytes(), modify))
+        streams.append(orc.nybble_compress(bytes(rng.integers(1, 128, size=3000, dtype=np.uint8)), modify))
+        streams.append(bytes([0x41]) + b"raw bytes under another type")
+        streams.append(bytes([0xAF]) + rng.integers(0, 256, size=777, dtype=np.uint8).tobytes())
+        streams.append(bytes([0xAF]))
+        for _ in range(300):
+            n = int(rng.integers(1, 2000))
+            streams.append(orc.nybble_compress(synth.english_like(n, seed=int(rng.integers(1 << 30))).tobytes(), modify))
+        want = [b"" if st == b"" else orc.nybble_decompress(st, modify) if st[0] != 0xAF or len(st) >= 2 else b""
+                for st in streams]
+        res[modify] = (streams, want)
+    return res
+
+
+@pytest.mark.parametrize("modify", MODES)
+def test_async_decode_of_mixed_types_vs_oracle(torch_cuda, codec, mixed_streams, modify):
+    streams, want = mixed_streams[modify]
+    assert {s[0] for s in streams if s} >= {0xAF, 0x20, 0x41} and bytes([0xAF]) in streams
+    h, starts, ends = _decode_gapped(torch_cuda, codec, streams, [len(w) for w in want], modify, (modify,))
+    for i, w in enumerate(want):
+        assert h[starts[i]: ends[i]].tobytes() == w, (modify, i, len(streams[i]))
+
+
+@pytest.mark.parametrize("modify", MODES)
+@pytest.mark.parametrize("delta", (1, -1))
+def test_wrong_asked_length_fails_alone(torch_cuda, codec, delta, modify):
+    """A nybble stream (buffer 66: 4095 bytes of text) and a LITERAL stream (the 100 random
+    bytes) asked for one byte more or less than they hold: DC_E_STREAM for exactly those two."""
+    streams = oracle_streams(STREAM_INPUTS, modify)
+    i_nyb, i_lit = 66, I_RANDOM_100
+    assert streams[i_nyb][0] == 0xAF and streams[i_lit][0] == 0x20
+    pick = list(range(40, 110))   # more than one wave, around both
+    sub = [streams[i] for i in pick]
+    lens = [STREAM_INPUTS[i].size for i in pick]
+    bad = {}
+    for i in (i_nyb, i_lit):
+        lens[pick.index(i)] += delta
+        bad[pick.index(i)] = DC_E_STREAM
+    dec_high, high_fits = _high_outcome(modify)
+    if not high_fits:
+        bad[pick.index(I_HIGH)] = DC_E_STREAM
+    h, starts, ends = _decode_gapped(torch_cuda, codec, sub, lens, modify, (delta, modify), bad=bad)
+    for p, i in enumerate(pick):
+        if p not in bad:
+            want = dec_high if i == I_HIGH else STREAM_INPUTS[i].tobytes()
+            assert h[starts[p]: ends[p]].tobytes() == want, (delta, modify, i)
+
+
+@pytest.mark.parametrize("modify", MODES)
+def test_blocks_are_the_chunk_streams_of_the_container(torch_cuda, codec, modify):
+    """nyb_compress_blocks at 4096 against the DCNK container of the same K: the same streams at
+    the same offsets (container: 32-B header, u64 off[nchunks + 1], payload)."""
+    torch = torch_cuda
+    from data_compression_amd import synth
+    x = _dev(torch, synth.english_like(300_007, seed=17))
+    K = 4096
+    nch = (300_007 + K - 1) // K
+    box = codec.nyb_compress_chunked(x, modify, K).cpu().numpy()
+    assert box[:4].tobytes() == b"DCNK" and int(box[24:32].view(np.uint64)[0]) == nch
+    c_off = box[32: 32 + 8 * (nch + 1)].view(np.uint64).astype(np.int64)
+    payload = box[32 + 8 * (nch + 1):]
+    out = torch.full((codec.nyb_batch_bound(300_007, nch) + 48,), FILL, dtype=torch.uint8, device="cuda")
+    o, oo, st = codec.nyb_compress_blocks(x, K, modify, out=out)
+    assert codec.batch_status() == 0 and (st.cpu().numpy() == 0).all() and st.numel() == nch
+    assert np.array_equal(oo.cpu().numpy(), c_off)
+    h = o.cpu().numpy()
+    assert np.array_equal(h[: c_off[-1]], payload[: c_off[-1]]) and payload.size == c_off[-1]
+    assert (h[c_off[-1]:] == FILL).all()
