@@ -7992,6 +7992,10 @@ int dc_nyb_body_write(dc_ctx *c, const uint8_t *d_in, uint64_t len, int modify, 
     FsmAux aux{adaptive ? c->d_rk : nullptr, pend_rank < 0 ? 0u : (uint32_t)pend_rank,
                pend_rank < 0 ? 0u : 1u, is_last ? 1u : 0u, 0, 0, adaptive ? c->d_mrec : nullptr,
                adaptive ? mtf_heads(c, len) : nullptr};
+    // a shard of no elements that ends the stream while a nybble is pending: the odd-tail byte is
+    // the pending byte itself, d_in[0] (the writers' odd tail is an element of the shard, len >= 2)
+    if (len == 1 && is_last && pend_rank >= 0)
+        HIPCHK(hipMemcpyAsync(d_out, d_in, 1, hipMemcpyDeviceToDevice, c->stream));
     int r = fsm_run<M_NYB_ENC>(c, d_in, len, len - 1, d_out, h_len, "nyb_body_tiles", aux, nullptr, true, nullptr,
                                0, modify && len > 1);
     if (r) return r;

@@ -647,6 +647,9 @@ int dc_nyb_decompress_batch_async(dc_ctx *ctx, const uint8_t *d_in, const uint64
  *     rank, or -1), the odd-tail byte when is_last; no header and no LITERAL fallback (decided
  *     over the whole stream). The adaptive ranks come from the preceding dc_nyb_body_plan on
  *     the same d_in/len. d_out capacity >= 2*len. *h_state_out = exit state.
+ *     A shard of no elements (len = 1) leaves the state as it entered: it writes nothing, but
+ *     for the one byte d_in[0] (the byte whose nybble is pending) when is_last and
+ *     pend_rank >= 0, the stream's odd tail.
  * Static decode of a shard of the compressed stream after its 2-byte header: m bytes, plus
  * one byte of right halo (the next shard's first byte) when len = m + 1:
  *   dc_nyb_dbody_plan: h_plan[0..3] as above (state 1 = start at the low nybble);

@@ -256,6 +256,12 @@ class CpuEngine:
         out, _ = self._walk(a, rk, 1 if pend_rank >= 0 else 0, pend_rank, is_last)
         return torch.from_numpy(np.frombuffer(bytes(head) + out, np.uint8).copy())
 
+    def nyb_body_state(self, pend_rank):
+        """Exit state of nyb_body_write on the planned shard (dc_nyb_body_write's *h_state_out):
+        is the last element's hit nybble pending."""
+        a, rk = self._plan
+        return self._walk(a, rk, 1 if pend_rank >= 0 else 0, pend_rank, False)[1]
+
     def _dwalk(self, a, m, s):
         out = bytearray()
         for k in range(m):
