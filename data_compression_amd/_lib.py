@@ -161,6 +161,9 @@ def _declare_core(L):
         "dc_nyb_dbody_write": ([vp, P, u64, u64, i32, P, C.POINTER(u64), C.POINTER(i32)], i32),
         "dc_small_compress": ([vp, P, u64, P, C.POINTER(u64)], i32),
         "dc_small_decompress": ([vp, P, u64, P, C.POINTER(u64)], i32),
+        "dc_small_batch_bound": ([u64, u64], u64),
+        "dc_small_compress_batch": ([vp, P, P, u64, P, u64, P, P], i32),
+        "dc_small_decompress_batch": ([vp, P, P, u64, P, P, u64, P], i32),
         "dc_small_compress_body": ([vp, P, u64, i32, u64, P, C.POINTER(u64)], i32),
         "dc_small_compress_body_plan": ([vp, P, u64, i32, u64, C.POINTER(u64)], i32),
         "dc_small_compress_body_write": ([vp, P, u64, i32, u64, P, C.POINTER(u64)], i32),

@@ -19,6 +19,7 @@
 #include "dc_gpu.h"
 #include "dc_batch_bound.h"
 #include "dc_nyb_batch_bound.h"
+#include "dc_small_batch_bound.h"
 #include "dc_batch_range.h"
 
 #define DC_VERSION "dc-mi355x 0.1 (gfx950)"
@@ -6272,6 +6273,7 @@ __global__ __launch_bounds__(256) void k_copy_probe(const uint4 *__restrict__ sr
 #include "dc_batch_shared_kernels.inc"
 #include "dc_batch_range_kernels.inc"
 #include "dc_nyb_batch_kernels.inc"
+#include "dc_small_batch_kernels.inc"
 
 #ifdef DC_AB_KERNELS
 #include "dc_ab_kernels.inc"
@@ -7923,6 +7925,40 @@ int dc_nyb_decompress_batch_async(dc_ctx *c, const uint8_t *d_in, const uint64_t
     if (const int r = hbatch_begin(c, count, &first)) return r;
     LAUNCH(c, "nyb_batch_dec_async", k_nyb_batch_dec_async, (count + 63) / 64, 64, d_in, d_in_off, d_out_off, count,
            modify ? 1 : 0, d_out, out_cap, d_status, first);
+    return DC_OK;
+}
+
+// ---- small batch v1 (dc_small_batch_kernels.inc) ---------------------------------------
+uint64_t dc_small_batch_bound(uint64_t total_bytes, uint64_t count) { return dc_small_batch_bound_calc(total_bytes, count); }
+
+int dc_small_compress_batch(dc_ctx *c, const uint8_t *d_in, const uint64_t *d_in_off, uint64_t count, uint8_t *d_out,
+                            uint64_t out_cap, uint64_t *d_out_off, int32_t *d_status)
+{
+    if (!c) return DC_E_ARG;
+    if (count == 0) return DC_OK;
+    if (count > DC_RANGES_MAX || !d_in || !d_in_off || !d_out || !d_out_off || !d_status) return DC_E_ARG;
+    unsigned long long *first;
+    if (const int r = hbatch_begin(c, count, &first)) return r;
+    uint64_t *const lens = c->d_hb + 2;
+    const uint64_t grid = hbatch_grid(c, (count + SB_WAVES - 1) / SB_WAVES, 2048);   // a wave per buffer, 8 workgroups per CU
+    LAUNCH(c, "small_batch_len", k_small_batch_len, grid, SB_THREADS, d_in, d_in_off, count, lens);
+    LAUNCH(c, "small_batch_scan", k_scan_u64, 1, 1024, (const uint64_t *)lens, count, d_out_off);
+    LAUNCH(c, "small_batch_enc", k_small_batch_enc, grid, SB_THREADS, d_in, d_in_off, (const uint64_t *)d_out_off, count,
+           d_out, out_cap, d_status, first);
+    return DC_OK;
+}
+
+int dc_small_decompress_batch(dc_ctx *c, const uint8_t *d_in, const uint64_t *d_in_off, uint64_t count, uint8_t *d_out,
+                              const uint64_t *d_out_off, uint64_t out_cap, int32_t *d_status)
+{
+    if (!c) return DC_E_ARG;
+    if (count == 0) return DC_OK;
+    if (count > DC_RANGES_MAX || !d_in || !d_in_off || !d_out || !d_out_off || !d_status) return DC_E_ARG;
+    unsigned long long *first;
+    if (const int r = hbatch_begin(c, count, &first)) return r;
+    const uint64_t grid = hbatch_grid(c, (count + SB_WAVES - 1) / SB_WAVES, 2048);
+    LAUNCH(c, "small_batch_dec", k_small_batch_dec, grid, SB_THREADS, d_in, d_in_off, d_out_off, count, d_out, out_cap,
+           d_status, first);
     return DC_OK;
 }
 

@@ -286,6 +286,77 @@ class Codec:
                                                                           _ptr(out), C.byref(n)))
         return out[: n.value]
 
+    def small_compress(self, x, out=None):
+        """dc_small_compress: the front-end stream of device bytes x (one stream, one host read
+        of its length), into `out` when given: at least x.numel() + 64 bytes."""
+        if out is None:
+            out = self._t(x.numel() + 64)
+        elif out.numel() < x.numel() + 64 or out.dtype != torch.uint8 or not out.is_contiguous():
+            raise ValueError("small_compress output: contiguous uint8 of >= x.numel() + 64 bytes")
+        n = C.c_uint64(0)
+        check("dc_small_compress", self.L.dc_small_compress(self.ctx, _ptr(x), x.numel(), _ptr(out), C.byref(n)))
+        return out[: n.value]
+
+    # ---- small batch v1: many buffers, one call each way (dc_gpu.h "small batch v1") -----------
+    def small_batch_bound(self, total: int, count: int) -> int:
+        """Bytes that always hold the streams of `count` buffers of `total` bytes in all
+        (dc_small_batch_bound: total + count, exact)."""
+        return int(self.L.dc_small_batch_bound(total, count))
+
+    def small_compress_batch(self, x, offsets, out=None, out_cap: int | None = None):
+        """dc_small_compress_batch: buffer i = x[offsets[i]:offsets[i+1]] (device uint8 x, int64
+        offsets of count + 1 entries, any alignment, any length) coded as the front-end stream of
+        that buffer alone (what small_compress gives for it), the streams back to back in `out`.
+        Asynchronous, no host read; the launches do not depend on count or on the lengths.
+        out: an optional preallocated uint8 buffer (else small_batch_bound(x.numel(), count)
+        bytes); out_cap: a smaller capacity to hand to the kernels. Returns device tensors (out,
+        out_off, status): out_off (int64, count + 1) always holds the true stream offsets, status
+        (int32) each buffer's outcome; batch_status() gives the lowest failing buffer's."""
+        if x.dtype != torch.uint8 or not x.is_contiguous():
+            raise ValueError("small_compress_batch input: contiguous uint8")
+        offsets = self._i64(offsets, range(1, 1 << 62), "small_compress_batch offsets")
+        count = offsets.numel() - 1
+        if out is None:
+            out = self._t(max(self.small_batch_bound(x.numel(), count), 1))
+        buf = self._u8_out(out, "small_compress_batch")
+        cap = buf.numel() if out_cap is None else min(int(out_cap), buf.numel())
+        out_off = self._t(count + 1, torch.int64) if count else torch.zeros(1, dtype=torch.int64, device=x.device)
+        status = self._t(max(count, 1), torch.int32)[:count]
+        check("dc_small_compress_batch",
+              self.L.dc_small_compress_batch(self.ctx, _ptr(x), _ptr(offsets), count, _ptr(buf), cap, _ptr(out_off),
+                                             _ptr(status)))
+        return out, out_off, status
+
+    def small_compress_blocks(self, x, block: int, **kw):
+        """small_compress_batch of x cut into independent blocks of `block` bytes (the last
+        shorter), the offsets made on the device."""
+        if block <= 0:
+            raise ValueError("small_compress_blocks: block > 0")
+        n = x.numel()
+        off = torch.arange(0, n + block, block, dtype=torch.int64, device=x.device).clamp_(max=n)
+        return self.small_compress_batch(x, off[: (n + block - 1) // block + 1].contiguous(), **kw)
+
+    def small_decompress_batch_into(self, data, offsets, out_off, out=None):
+        """dc_small_decompress_batch: stream i = data[offsets[i]:offsets[i+1]] decoded into
+        out[out_off[i]:out_off[i+1]] (int64 device tensors or sequences of count + 1 entries; the
+        length asked for must be the stream's). Asynchronous, one launch, no host read unless
+        `out` is left to default, which reads out_off[-1] once to size it. Returns device tensors
+        (out, status); a stream of any status but 0 writes no byte, and no byte outside the asked
+        ranges is written."""
+        if data.dtype != torch.uint8 or not data.is_contiguous():
+            raise ValueError("small_decompress_batch_into input: contiguous uint8")
+        offsets = self._i64(offsets, range(1, 1 << 62), "small_decompress_batch_into offsets")
+        count = offsets.numel() - 1
+        out_off = self._i64(out_off, (count + 1,), "small_decompress_batch_into out_off")
+        if out is None:
+            out = self._t(max(int(out_off[-1]), 1))
+        buf = self._u8_out(out, "small_decompress_batch_into")
+        status = self._t(max(count, 1), torch.int32)[:count]
+        check("dc_small_decompress_batch",
+              self.L.dc_small_decompress_batch(self.ctx, _ptr(data), _ptr(offsets), count, _ptr(buf), _ptr(out_off),
+                                               buf.numel(), _ptr(status)))
+        return out, status
+
     # ---- nybble codec, whole streams and shard bodies (SURVEY §8(e); dist.ShardedNybble) -----
     def nyb_compress(self, x, modify: bool, out=None):
         """compress_bytestring (nybble_compression.c:887-1038) of device bytes x (into `out`
@@ -742,7 +813,8 @@ class Codec:
     def batch_status(self) -> int:
         """0, or the status of the lowest-numbered failing segment of the last batch call on this
         codec (encode_batch, decode_batch, decode_batch_ranges, nyb_compress_batch,
-        nyb_decompress_batch_into), synchronising."""
+        nyb_decompress_batch_into, small_compress_batch, small_decompress_batch_into),
+        synchronising."""
         return int(self.L.dc_huff_batch_status(self.ctx))
 
     # ---- C5 fused front-end encode (small_compression.c front-end, then Huffman; one pass) -----

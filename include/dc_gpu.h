@@ -668,6 +668,62 @@ int dc_small_compress(dc_ctx *ctx, const uint8_t *d_in, uint64_t n, uint8_t *d_o
                       uint64_t *h_out_len);
 int dc_small_decompress(dc_ctx *ctx, const uint8_t *d_in, uint64_t m, uint8_t *d_out,
                         uint64_t *h_out_len);
+/* ---- small batch v1: many buffers of their own lengths, one call each way ---------------------
+ * The format is nothing but the front-end's own streams back to back plus their offsets: no
+ * header, no container. Both calls are asynchronous on the context's stream, make no host read,
+ * and launch the same kernels for any count and any lengths, so a round trip can be enqueued or
+ * captured (the first call at a larger count grows the context's 16 B of scratch per buffer).
+ * count 0 returns DC_OK without a launch; count > DC_RANGES_MAX, a NULL context or (with
+ * count > 0) any NULL pointer returns DC_E_ARG. A bad buffer never stops the others.
+ * d_status[i] (i32, count entries) receives each buffer's outcome, and dc_huff_batch_status
+ * (the context keeps one first-failure slot for every batch call) reports the lowest failing
+ * index of the last such call, synchronising. DC_OPT_BATCH_GRID sizes the grids.
+ *
+ * dc_small_batch_bound = total_bytes + count: a buffer of len >= 1 bytes codes to at most len + 1
+ * bytes (the LITERAL form), an empty one to the single byte ' '. Exact, and pure host arithmetic
+ * (csrc/dc_small_batch_bound.h).
+ *
+ * dc_small_compress_batch: buffer i = d_in[d_in_off[i] .. d_in_off[i+1]) (device u64, count + 1
+ * entries; any alignment, any length, 0 too). Stream i is exactly what dc_small_compress writes
+ * for that buffer alone. With P = the positions i >= 1, i + 1 < len, that hold ' ' before a..z:
+ * for P >= 2 the pruned form (the type byte 8, the raw first byte, then every byte as itself but a
+ * pair as the one byte 0x80 + letter: len + 1 - P bytes), else the LITERAL form (' ' and the
+ * bytes), ' ' alone for length 0. All 256 byte values are in the domain, 0 included. The streams
+ * lie back to back in d_out: the call writes d_out_off[0] = 0 and d_out_off[i+1] = d_out_off[i] +
+ * (length of stream i), count + 1 entries, always the true lengths, so d_out_off[count] is the
+ * capacity the batch needs even when out_cap was too small.
+ *   DC_E_ARG       the buffer's offsets decrease: it takes 0 output bytes, and nothing of it is
+ *                  read or written
+ *   DC_E_CAPACITY  d_out_off[i+1] > out_cap: nothing of it is written
+ * Nothing is ever written at or past d_out + out_cap, and no byte of d_out that belongs to no
+ * good stream is written.
+ * Cost: three launches, a count pass (P -> the stream's length), a scan and a write pass straight
+ * to the final place (it knows the form from the length: len + 1 is LITERAL). One WAVE codes one
+ * buffer, in tiles of 1 KiB, and takes buffers in a fixed stride: 64 unequal buffers do not wait
+ * for the longest one, but a batch of very unequal lengths runs faster sorted by length, which
+ * shares the long buffers evenly among the waves (tools/small_batch_bench.py records the
+ * difference). A buffer is never split between waves: buffers of many MiB belong in
+ * dc_small_compress, which spreads one stream over the device. There is no maximum buffer length.
+ *
+ * dc_small_decompress_batch: stream i = d_in[d_in_off[i] .. d_in_off[i+1]) is decoded into
+ * d_out[d_out_off[i] .. d_out_off[i+1]), where the CALLER gives d_out_off (count + 1 entries): the
+ * format stores no length, so the length asked for must be the stream's. The type dispatch is
+ * dc_small_decompress's: type 8 with m >= 2 bytes gives byte 1 raw, then ' ', b - 0x80 for every
+ * later byte b >= 0x80 and b itself otherwise; ' ' gives the m - 1 bytes after it; an empty stream,
+ * a lone type 8 and any other type byte give nothing (length 0). One launch.
+ *   DC_E_ARG       either offset pair decreases: nothing is read or written
+ *   DC_E_CAPACITY  d_out_off[i+1] > out_cap
+ *   DC_E_STREAM    the stream does not decode to exactly the asked length
+ * A stream with any status but DC_OK writes NO byte (the decoded length is a count over the
+ * stream: the kernel counts first and writes only when it matches), and no byte outside a good
+ * stream's own range is ever written. A pruned stream that holds a raw input byte >= 0x80 after
+ * position 0 decodes to more bytes than went in (the reference's own limit): asked at its input
+ * length it is DC_E_STREAM, never wrong bytes. */
+uint64_t dc_small_batch_bound(uint64_t total_bytes, uint64_t count);
+int dc_small_compress_batch(dc_ctx *ctx, const uint8_t *d_in, const uint64_t *d_in_off, uint64_t count,
+                            uint8_t *d_out, uint64_t out_cap, uint64_t *d_out_off, int32_t *d_status);
+int dc_small_decompress_batch(dc_ctx *ctx, const uint8_t *d_in, const uint64_t *d_in_off, uint64_t count,
+                              uint8_t *d_out, const uint64_t *d_out_off, uint64_t out_cap, int32_t *d_status);
 /* Shard bodies (data_compression_amd/dist.py ShardedSmall): the front-end
  * output of stream bytes d_in[1 .. nelem] (no header, no LITERAL fallback), reading d_in[0]
  * as left context when left_halo (a shard after the first: d_in[0] = the previous shard's
