@@ -5985,8 +5985,72 @@ static __device__ __forceinline__ void nl_walk(const uint4 *g, uint64_t lo, uint
     }
 }
 
+// One lane's walk of its buffer x[0 .. len) (every lane of the wave calls it; a lane without a
+// buffer passes len = 0, cap = 0, literal = false). STORE = false: returns the stream's length
+// (the nybble form's bytes q, or len + 1 when q >= len: the LITERAL form, :1018-1037; 1 for
+// len 0) and touches no output. STORE = true: puts the stream (the form given by `literal`)
+// through o, of which never more than cap bytes leave for memory, and returns the bytes put.
+template <bool STORE>
+static __device__ __forceinline__ uint64_t nyb_lane_encode(const uint8_t *__restrict__ x, uint64_t len, int modify,
+                                                           bool literal, uint64_t cap, NlOut &o, uint64_t (*sL)[64],
+                                                           int t)
+{
+    for (int c = 0; c < 16; ++c) sL[c][t] = mtf_init_word();
+    uint64_t q = 0;   // bytes put
+    auto put = [&](uint32_t v) {
+        if (STORE) o.ring[(o.sh + q) & (NL_ORING - 1)] = (uint8_t)v;   // (LDS, the index masked)
+        ++q;
+    };
+    // what may leave for memory: the bytes put, never more than cap (tested at the points, not per
+    // byte: q == cap at the end whenever the input is what the length walk saw)
+    auto sent = [&]() { return o.sh + (q < cap ? q : cap); };
+    uint32_t prev = len ? x[0] : 0u;
+    if (STORE && literal) put(' ');
+    else if (len) put(0xAF);
+    if (len) put(prev);
+    int half = 0;
+    uint32_t hi = 0;   // pending high nybble
+    const uintptr_t xa = (uintptr_t)x;
+    const uint4 *g = len > 1 ? reinterpret_cast<const uint4 *>(x - (xa & 15)) : nl_zero;
+    const uint64_t sh = len > 1 ? xa & 15 : 0;
+    nl_walk(g, len > 1 ? sh + 1 : 0, len > 1 ? sh + len : 0,
+        [&](uint32_t v, bool valid) {
+            if (valid) {
+                const uint32_t c = (prev >> 3) & 15u;
+                uint32_t pb;
+                bool hit;
+                // compress_byte_index :833-839 (rank before the touch), update_context :665-687
+                const uint64_t L = mtf_touch8(sL[c][t], v, pb, hit);
+                if (modify) sL[c][t] = L;
+                if (STORE && literal) hit = false;   // the LITERAL form: every byte goes as a miss does, raw
+                if (!hit) {
+                    if (half) { put(prev); half = 0; }   // miss at offset 1 (:855-857)
+                    put(v);
+                } else if (!half) {
+                    hi = (8u | (pb >> 3)) << 4;
+                    half = 1;
+                } else {
+                    put(hi | 8u | (pb >> 3));
+                    half = 0;
+                }
+                prev = v;
+            }
+        },
+        [&]() { if (STORE) nl_out_point(o, sent()); });
+    if (half) put(prev);   // odd tail (:1000-1009): the last byte raw
+    if (!STORE) return q >= len ? len + 1 : q;
+    nl_out_point(o, sent());
+    nl_out_finish(o, sent());
+    return q;
+}
+
 // DCNK encode: one lane per chunk of K bytes, nybble_compress of the chunk
-// (compress_bytestring, nybble_compression.c:887-1038) into its scratch slot of K + 2 bytes
+// (compress_bytestring, nybble_compression.c:887-1038) into its scratch slot of K + 2 bytes.
+// The walk is nyb_lane_encode<true>'s with literal = false, written out: as a call of it, under a
+// cap that never binds (len + 2), this kernel took 1.057 ms against 1.026 on 65 536 chunks of
+// 4 KiB (profiles/stream_batch_frame_ab.log: the min(q, cap) at every output point), three times
+// the spread of that comparison. A change to either walk belongs in both;
+// test_container_chunks_are_the_batch_streams_at_every_edge holds their streams equal.
 __global__ __launch_bounds__(64) void k_nyb_chunk_enc(const uint8_t *__restrict__ in, uint64_t n, uint32_t K,
                                                       uint64_t nchunks, int modify, uint8_t *__restrict__ scr,
                                                       uint64_t *__restrict__ lens)
@@ -7895,17 +7959,26 @@ int dc_nyb_decompress_batch(dc_ctx *c, const uint8_t *d_in, const uint64_t *d_in
     return c->h_pinned[0] ? DC_E_STREAM : DC_OK;
 }
 
+// ---- byte-stream batch v1 (dc_gpu.h): what the four nybble and small batch calls begin with ----
+// 1 (nothing to do), 0 with d_hb sized for `count` lengths and the first-failure slot turned over,
+// or an error.
+static int sbatch_begin(dc_ctx *c, const uint8_t *d_in, const uint64_t *d_in_off, uint64_t count, const uint8_t *d_out,
+                        const uint64_t *d_out_off, const int32_t *d_status, unsigned long long **first)
+{
+    if (!c) return DC_E_ARG;
+    if (count == 0) return 1;
+    if (count > DC_RANGES_MAX || !d_in || !d_in_off || !d_out || !d_out_off || !d_status) return DC_E_ARG;
+    return hbatch_begin(c, count, first);
+}
+
 // ---- nybble batch v1 (dc_nyb_batch_kernels.inc) ----------------------------------------
 uint64_t dc_nyb_batch_bound(uint64_t total_bytes, uint64_t count) { return dc_nyb_batch_bound_calc(total_bytes, count); }
 
 int dc_nyb_compress_batch(dc_ctx *c, const uint8_t *d_in, const uint64_t *d_in_off, uint64_t count, int modify,
                           uint8_t *d_out, uint64_t out_cap, uint64_t *d_out_off, int32_t *d_status)
 {
-    if (!c) return DC_E_ARG;
-    if (count == 0) return DC_OK;
-    if (count > DC_RANGES_MAX || !d_in || !d_in_off || !d_out || !d_out_off || !d_status) return DC_E_ARG;
     unsigned long long *first;
-    if (const int r = hbatch_begin(c, count, &first)) return r;
+    if (const int r = sbatch_begin(c, d_in, d_in_off, count, d_out, d_out_off, d_status, &first)) return r > 0 ? DC_OK : r;
     uint64_t *const lens = c->d_hb + 2;
     const uint64_t grid = (count + 63) / 64;
     LAUNCH(c, "nyb_batch_enc_len", k_nyb_batch_enc_len, grid, 64, d_in, d_in_off, count, modify ? 1 : 0, lens);
@@ -7918,11 +7991,8 @@ int dc_nyb_compress_batch(dc_ctx *c, const uint8_t *d_in, const uint64_t *d_in_o
 int dc_nyb_decompress_batch_async(dc_ctx *c, const uint8_t *d_in, const uint64_t *d_in_off, uint64_t count, int modify,
                                   uint8_t *d_out, const uint64_t *d_out_off, uint64_t out_cap, int32_t *d_status)
 {
-    if (!c) return DC_E_ARG;
-    if (count == 0) return DC_OK;
-    if (count > DC_RANGES_MAX || !d_in || !d_in_off || !d_out || !d_out_off || !d_status) return DC_E_ARG;
     unsigned long long *first;
-    if (const int r = hbatch_begin(c, count, &first)) return r;
+    if (const int r = sbatch_begin(c, d_in, d_in_off, count, d_out, d_out_off, d_status, &first)) return r > 0 ? DC_OK : r;
     LAUNCH(c, "nyb_batch_dec_async", k_nyb_batch_dec_async, (count + 63) / 64, 64, d_in, d_in_off, d_out_off, count,
            modify ? 1 : 0, d_out, out_cap, d_status, first);
     return DC_OK;
@@ -7934,11 +8004,8 @@ uint64_t dc_small_batch_bound(uint64_t total_bytes, uint64_t count) { return dc_
 int dc_small_compress_batch(dc_ctx *c, const uint8_t *d_in, const uint64_t *d_in_off, uint64_t count, uint8_t *d_out,
                             uint64_t out_cap, uint64_t *d_out_off, int32_t *d_status)
 {
-    if (!c) return DC_E_ARG;
-    if (count == 0) return DC_OK;
-    if (count > DC_RANGES_MAX || !d_in || !d_in_off || !d_out || !d_out_off || !d_status) return DC_E_ARG;
     unsigned long long *first;
-    if (const int r = hbatch_begin(c, count, &first)) return r;
+    if (const int r = sbatch_begin(c, d_in, d_in_off, count, d_out, d_out_off, d_status, &first)) return r > 0 ? DC_OK : r;
     uint64_t *const lens = c->d_hb + 2;
     const uint64_t grid = hbatch_grid(c, (count + SB_WAVES - 1) / SB_WAVES, 2048);   // a wave per buffer, 8 workgroups per CU
     LAUNCH(c, "small_batch_len", k_small_batch_len, grid, SB_THREADS, d_in, d_in_off, count, lens);
@@ -7951,11 +8018,8 @@ int dc_small_compress_batch(dc_ctx *c, const uint8_t *d_in, const uint64_t *d_in
 int dc_small_decompress_batch(dc_ctx *c, const uint8_t *d_in, const uint64_t *d_in_off, uint64_t count, uint8_t *d_out,
                               const uint64_t *d_out_off, uint64_t out_cap, int32_t *d_status)
 {
-    if (!c) return DC_E_ARG;
-    if (count == 0) return DC_OK;
-    if (count > DC_RANGES_MAX || !d_in || !d_in_off || !d_out || !d_out_off || !d_status) return DC_E_ARG;
     unsigned long long *first;
-    if (const int r = hbatch_begin(c, count, &first)) return r;
+    if (const int r = sbatch_begin(c, d_in, d_in_off, count, d_out, d_out_off, d_status, &first)) return r > 0 ? DC_OK : r;
     const uint64_t grid = hbatch_grid(c, (count + SB_WAVES - 1) / SB_WAVES, 2048);
     LAUNCH(c, "small_batch_dec", k_small_batch_dec, grid, SB_THREADS, d_in, d_in_off, d_out_off, count, d_out, out_cap,
            d_status, first);

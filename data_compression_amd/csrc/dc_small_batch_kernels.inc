@@ -1,8 +1,8 @@
 // dc_small_batch_kernels.inc -- small batch v1 (dc_gpu.h): many independent buffers, each coded as
 // the small front-end's stream of that buffer alone (small_compression.c:582-665), back to back,
 // and the asynchronous decode of such a batch. Included by dc_core.hip after
-// dc_nyb_batch_kernels.inc (swar_eq / swar_lower, the DPP wave shifts and scans, hb_fail:
-// status[i] and the context's first-failure slot).
+// dc_nyb_batch_kernels.inc (swar_eq / swar_lower, the DPP wave shifts and scans; bs_item /
+// bs_report: the per-buffer frame, status[i] and the context's first-failure slot).
 //
 // Whether position i starts a pair depends on x[i] and x[i + 1] alone (' ' then a..z, i >= 1; a
 // letter is never ' ', so pairs cannot overlap): the encode is a stream compaction, the decode a
@@ -251,19 +251,17 @@ __global__ __launch_bounds__(SB_THREADS) void k_small_batch_enc(const uint8_t *_
     const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     uint8_t *const stage = s_stage[w];
     for (uint64_t i = (uint64_t)blockIdx.x * SB_WAVES + w; i < count; i += (uint64_t)gridDim.x * SB_WAVES) {
-        const uint64_t a = in_off[i], b = in_off[i + 1];
-        const uint64_t o0 = out_off[i], o1 = out_off[i + 1];
-        const int st = b < a ? DC_E_ARG : (o1 > out_cap || o1 < o0) ? DC_E_CAPACITY : DC_OK;
-        if (st != DC_OK) {
-            if (lane == 0) hb_fail(status, first, i, st);
+        const BsItem E = bs_item<false>(in_off, out_off, i, true, out_cap);
+        if (!E.good) {
+            bs_report(status, first, i, E.st, lane == 0);
             continue;
         }
-        const uint64_t n = b - a;
-        const bool literal = o1 - o0 == n + 1;
-        SbOut O = sb_out(out + o0, o1 - o0);
+        const uint64_t n = E.n;
+        const bool literal = E.room == n + 1;
+        SbOut O = sb_out(out + E.o0, E.room);
         if (lane == 0) stage[O.fill] = literal ? (uint8_t)' ' : (uint8_t)SB_PRUNED;   // the type byte
         O.fill += 1;
-        sb_walk(sb_buf(in + a, n), lane, [&](const SbTile &T, const uint4 &c, uint32_t p, uint32_t q, bool last) {
+        sb_walk(sb_buf(in + E.a, n), lane, [&](const SbTile &T, const uint4 &c, uint32_t p, uint32_t q, bool last) {
             uint32_t val[4], keep[4], pr = 0;
             uint32_t cnt = sb_classify(T, c, p, q, lane, val, keep, pr);
             if (literal) {   // every byte of the buffer as it is
@@ -292,7 +290,7 @@ __global__ __launch_bounds__(SB_THREADS) void k_small_batch_enc(const uint8_t *_
         });
         if (n == 0) sb_flush(stage, O, true, lane);   // (no tile: the type byte alone)
         __builtin_amdgcn_wave_barrier();               // the stage is rewritten by the next buffer
-        if (lane == 0) status[i] = DC_OK;
+        bs_report(status, first, i, DC_OK, lane == 0);
     }
 }
 
@@ -336,14 +334,13 @@ __global__ __launch_bounds__(SB_THREADS) void k_small_batch_dec(const uint8_t *_
     const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     uint8_t *const stage = s_stage[w];
     for (uint64_t i = (uint64_t)blockIdx.x * SB_WAVES + w; i < count; i += (uint64_t)gridDim.x * SB_WAVES) {
-        const uint64_t a = in_off[i], b = in_off[i + 1];
-        const uint64_t o0 = out_off[i], o1 = out_off[i + 1];
-        int st = (b < a || o1 < o0) ? DC_E_ARG : o1 > out_cap ? DC_E_CAPACITY : DC_OK;
-        if (st == DC_OK) {
-            const uint64_t m = b - a, want = o1 - o0;
-            const uint32_t type = m ? in[a] : 0x100u;
+        const BsItem E = bs_item<true>(in_off, out_off, i, true, out_cap);
+        int st = E.st;
+        if (E.good) {
+            const uint64_t m = E.n, want = E.room;
+            const uint32_t type = m ? in[E.a] : 0x100u;
             const bool pruned = type == SB_PRUNED, literal = type == ' ';
-            const SbBuf B = sb_buf(in + a, m);
+            const SbBuf B = sb_buf(in + E.a, m);
             uint64_t have = 0;
             if (literal) have = m - 1;
             else if (pruned) {
@@ -356,7 +353,7 @@ __global__ __launch_bounds__(SB_THREADS) void k_small_batch_dec(const uint8_t *_
             }
             if (have != want) st = DC_E_STREAM;
             else if (want) {
-                SbOut O = sb_out(out + o0, want);
+                SbOut O = sb_out(out + E.o0, want);
                 sb_walk(B, lane, [&](const SbTile &T, const uint4 &c, uint32_t, uint32_t, bool last) {
                     uint32_t emit[4], two[4];
                     const uint32_t cnt = sb_dec_classify(T, c, lane, pruned, emit, two);
@@ -385,9 +382,6 @@ __global__ __launch_bounds__(SB_THREADS) void k_small_batch_dec(const uint8_t *_
                 __builtin_amdgcn_wave_barrier();   // the stage is rewritten by the next stream
             }
         }
-        if (lane == 0) {
-            if (st == DC_OK) status[i] = DC_OK;
-            else hb_fail(status, first, i, st);
-        }
+        bs_report(status, first, i, st, lane == 0);
     }
 }

@@ -297,6 +297,44 @@ class Codec:
         check("dc_small_compress", self.L.dc_small_compress(self.ctx, _ptr(x), x.numel(), _ptr(out), C.byref(n)))
         return out[: n.value]
 
+    # ---- byte-stream batch v1: what the small and the nybble batch calls share (dc_gpu.h) ------
+    @staticmethod
+    def _block_offsets(x, block: int):
+        """The offsets of x cut into blocks of `block` bytes (the last shorter), made on the device."""
+        n = x.numel()
+        off = torch.arange(0, n + block, block, dtype=torch.int64, device=x.device).clamp_(max=n)
+        return off[: (n + block - 1) // block + 1].contiguous()
+
+    def _stream_compress_batch(self, name, fn, bound, lead, x, offsets, out, out_cap):
+        """fn(ctx, x, offsets, count, *lead, out, cap, out_off, status): the encode of either codec."""
+        if x.dtype != torch.uint8 or not x.is_contiguous():
+            raise ValueError(f"{name} input: contiguous uint8")
+        offsets = self._i64(offsets, range(1, 1 << 62), f"{name} offsets")
+        count = offsets.numel() - 1
+        if out is None:
+            out = self._t(max(bound(x.numel(), count), 1))
+        buf = self._u8_out(out, name)
+        cap = buf.numel() if out_cap is None else min(int(out_cap), buf.numel())
+        out_off = self._t(count + 1, torch.int64) if count else torch.zeros(1, dtype=torch.int64, device=x.device)
+        status = self._t(max(count, 1), torch.int32)[:count]
+        check(fn.__name__, fn(self.ctx, _ptr(x), _ptr(offsets), count, *lead, _ptr(buf), cap, _ptr(out_off), _ptr(status)))
+        return out, out_off, status
+
+    def _stream_decompress_batch(self, name, fn, lead, data, offsets, out_off, out):
+        """fn(ctx, data, offsets, count, *lead, out, out_off, cap, status): the decode of either codec."""
+        if data.dtype != torch.uint8 or not data.is_contiguous():
+            raise ValueError(f"{name} input: contiguous uint8")
+        offsets = self._i64(offsets, range(1, 1 << 62), f"{name} offsets")
+        count = offsets.numel() - 1
+        out_off = self._i64(out_off, (count + 1,), f"{name} out_off")
+        if out is None:
+            out = self._t(max(int(out_off[-1]), 1))
+        buf = self._u8_out(out, name)
+        status = self._t(max(count, 1), torch.int32)[:count]
+        check(fn.__name__, fn(self.ctx, _ptr(data), _ptr(offsets), count, *lead, _ptr(buf), _ptr(out_off), buf.numel(),
+                              _ptr(status)))
+        return out, status
+
     # ---- small batch v1: many buffers, one call each way (dc_gpu.h "small batch v1") -----------
     def small_batch_bound(self, total: int, count: int) -> int:
         """Bytes that always hold the streams of `count` buffers of `total` bytes in all
@@ -312,29 +350,15 @@ class Codec:
         bytes); out_cap: a smaller capacity to hand to the kernels. Returns device tensors (out,
         out_off, status): out_off (int64, count + 1) always holds the true stream offsets, status
         (int32) each buffer's outcome; batch_status() gives the lowest failing buffer's."""
-        if x.dtype != torch.uint8 or not x.is_contiguous():
-            raise ValueError("small_compress_batch input: contiguous uint8")
-        offsets = self._i64(offsets, range(1, 1 << 62), "small_compress_batch offsets")
-        count = offsets.numel() - 1
-        if out is None:
-            out = self._t(max(self.small_batch_bound(x.numel(), count), 1))
-        buf = self._u8_out(out, "small_compress_batch")
-        cap = buf.numel() if out_cap is None else min(int(out_cap), buf.numel())
-        out_off = self._t(count + 1, torch.int64) if count else torch.zeros(1, dtype=torch.int64, device=x.device)
-        status = self._t(max(count, 1), torch.int32)[:count]
-        check("dc_small_compress_batch",
-              self.L.dc_small_compress_batch(self.ctx, _ptr(x), _ptr(offsets), count, _ptr(buf), cap, _ptr(out_off),
-                                             _ptr(status)))
-        return out, out_off, status
+        return self._stream_compress_batch("small_compress_batch", self.L.dc_small_compress_batch,
+                                           self.small_batch_bound, (), x, offsets, out, out_cap)
 
     def small_compress_blocks(self, x, block: int, **kw):
         """small_compress_batch of x cut into independent blocks of `block` bytes (the last
         shorter), the offsets made on the device."""
         if block <= 0:
             raise ValueError("small_compress_blocks: block > 0")
-        n = x.numel()
-        off = torch.arange(0, n + block, block, dtype=torch.int64, device=x.device).clamp_(max=n)
-        return self.small_compress_batch(x, off[: (n + block - 1) // block + 1].contiguous(), **kw)
+        return self.small_compress_batch(x, self._block_offsets(x, block), **kw)
 
     def small_decompress_batch_into(self, data, offsets, out_off, out=None):
         """dc_small_decompress_batch: stream i = data[offsets[i]:offsets[i+1]] decoded into
@@ -343,19 +367,8 @@ class Codec:
         `out` is left to default, which reads out_off[-1] once to size it. Returns device tensors
         (out, status); a stream of any status but 0 writes no byte, and no byte outside the asked
         ranges is written."""
-        if data.dtype != torch.uint8 or not data.is_contiguous():
-            raise ValueError("small_decompress_batch_into input: contiguous uint8")
-        offsets = self._i64(offsets, range(1, 1 << 62), "small_decompress_batch_into offsets")
-        count = offsets.numel() - 1
-        out_off = self._i64(out_off, (count + 1,), "small_decompress_batch_into out_off")
-        if out is None:
-            out = self._t(max(int(out_off[-1]), 1))
-        buf = self._u8_out(out, "small_decompress_batch_into")
-        status = self._t(max(count, 1), torch.int32)[:count]
-        check("dc_small_decompress_batch",
-              self.L.dc_small_decompress_batch(self.ctx, _ptr(data), _ptr(offsets), count, _ptr(buf), _ptr(out_off),
-                                               buf.numel(), _ptr(status)))
-        return out, status
+        return self._stream_decompress_batch("small_decompress_batch_into", self.L.dc_small_decompress_batch, (), data,
+                                             offsets, out_off, out)
 
     # ---- nybble codec, whole streams and shard bodies (SURVEY §8(e); dist.ShardedNybble) -----
     def nyb_compress(self, x, modify: bool, out=None):
@@ -430,20 +443,8 @@ class Codec:
         out_cap: a smaller capacity to hand to the kernels. Returns device tensors (out, out_off,
         status): out_off (int64, count + 1) always holds the true stream offsets, status (int32)
         each buffer's outcome; batch_status() gives the lowest failing buffer's."""
-        if x.dtype != torch.uint8 or not x.is_contiguous():
-            raise ValueError("nyb_compress_batch input: contiguous uint8")
-        offsets = self._i64(offsets, range(1, 1 << 62), "nyb_compress_batch offsets")
-        count = offsets.numel() - 1
-        if out is None:
-            out = self._t(max(self.nyb_batch_bound(x.numel(), count), 1))
-        buf = self._u8_out(out, "nyb_compress_batch")
-        cap = buf.numel() if out_cap is None else min(int(out_cap), buf.numel())
-        out_off = self._t(count + 1, torch.int64) if count else torch.zeros(1, dtype=torch.int64, device=x.device)
-        status = self._t(max(count, 1), torch.int32)[:count]
-        check("dc_nyb_compress_batch",
-              self.L.dc_nyb_compress_batch(self.ctx, _ptr(x), _ptr(offsets), count, int(bool(modify)), _ptr(buf), cap,
-                                           _ptr(out_off), _ptr(status)))
-        return out, out_off, status
+        return self._stream_compress_batch("nyb_compress_batch", self.L.dc_nyb_compress_batch, self.nyb_batch_bound,
+                                           (int(bool(modify)),), x, offsets, out, out_cap)
 
     def nyb_compress_blocks(self, x, block: int, modify: bool, **kw):
         """nyb_compress_batch of x cut into independent blocks of `block` bytes (the last
@@ -451,9 +452,7 @@ class Codec:
         the same chunk size, without the container."""
         if block <= 0:
             raise ValueError("nyb_compress_blocks: block > 0")
-        n = x.numel()
-        off = torch.arange(0, n + block, block, dtype=torch.int64, device=x.device).clamp_(max=n)
-        return self.nyb_compress_batch(x, off[: (n + block - 1) // block + 1].contiguous(), modify, **kw)
+        return self.nyb_compress_batch(x, self._block_offsets(x, block), modify, **kw)
 
     def nyb_decompress_batch_into(self, data, offsets, modify: bool, out_off, out=None):
         """dc_nyb_decompress_batch_async: stream i = data[offsets[i]:offsets[i+1]] decoded into
@@ -462,19 +461,8 @@ class Codec:
         `out` is left to default, which reads out_off[-1] once to size it. Returns device tensors
         (out, status); a failed stream's own range holds unspecified bytes, and no byte outside
         the asked ranges is written."""
-        if data.dtype != torch.uint8 or not data.is_contiguous():
-            raise ValueError("nyb_decompress_batch_into input: contiguous uint8")
-        offsets = self._i64(offsets, range(1, 1 << 62), "nyb_decompress_batch_into offsets")
-        count = offsets.numel() - 1
-        out_off = self._i64(out_off, (count + 1,), "nyb_decompress_batch_into out_off")
-        if out is None:
-            out = self._t(max(int(out_off[-1]), 1))
-        buf = self._u8_out(out, "nyb_decompress_batch_into")
-        status = self._t(max(count, 1), torch.int32)[:count]
-        check("dc_nyb_decompress_batch_async",
-              self.L.dc_nyb_decompress_batch_async(self.ctx, _ptr(data), _ptr(offsets), count, int(bool(modify)),
-                                                   _ptr(buf), _ptr(out_off), buf.numel(), _ptr(status)))
-        return out, status
+        return self._stream_decompress_batch("nyb_decompress_batch_into", self.L.dc_nyb_decompress_batch_async,
+                                             (int(bool(modify)),), data, offsets, out_off, out)
 
     def nyb_mtf_summary(self, y):
         """Move-to-front lists after elements y[1..] from empty lists: (lists[16][8], cnt[16])."""
@@ -733,9 +721,7 @@ class Codec:
         table=..., all under that one table."""
         if not 0 < block <= self.SEG_MAX:
             raise ValueError("encode_blocks: 0 < block <= 65536")
-        n = x.numel()
-        off = torch.arange(0, n + block, block, dtype=torch.int64, device=x.device).clamp_(max=n)
-        return self.encode_batch(x, off[: (n + block - 1) // block + 1].contiguous(), **kw)
+        return self.encode_batch(x, self._block_offsets(x, block), **kw)
 
     def decode_batch(self, enc, out=None, out_off=None):
         """dc_huff_decode_batch of the dict encode_batch returned. out_off (int64 device tensor

@@ -577,33 +577,56 @@ int dc_nyb_decompress_chunked(dc_ctx *ctx, const uint8_t *d_in, uint64_t m, uint
  * offset range that ends before it starts. Synchronising. */
 int dc_nyb_decompress_batch(dc_ctx *ctx, const uint8_t *d_in, const uint64_t *d_in_off, uint64_t count, int modify,
                             uint8_t *d_out, uint64_t out_cap, uint64_t *d_out_off, uint64_t *h_total);
-/* ---- nybble batch v1: many buffers of their own lengths, one call each way -------------------
- * The format is nothing but the reference's own streams back to back plus their offsets: no
- * header, no container. Both calls are asynchronous on the context's stream, make no host read,
- * and launch the same kernels for any count and any lengths, so a round trip can be enqueued or
+/* ---- byte-stream batch v1: what the nybble and the small batch calls share ---------------------
+ * Two codecs, one shape (dc_nyb_* / dc_small_*: "nybble batch v1" and "small batch v1" below say
+ * what is their own: format, byte domain, cost, what a failed stream's range holds on decode). The
+ * format is nothing but the codec's own streams back to back plus their offsets: no header, no
+ * container. All four calls are asynchronous on the context's stream, make no host read, and
+ * launch the same kernels for any count and any lengths, so a round trip can be enqueued or
  * captured (the first call at a larger count grows the context's 16 B of scratch per buffer).
  * count 0 returns DC_OK without a launch; count > DC_RANGES_MAX, a NULL context or (with
  * count > 0) any NULL pointer returns DC_E_ARG. A bad buffer never stops the others.
  * d_status[i] (i32, count entries) receives each buffer's outcome, and dc_huff_batch_status
- * (there is no nybble twin: the context keeps one first-failure slot for every batch call)
- * reports the lowest failing index of the last such call, synchronising.
+ * (there is no nybble or small twin: the context keeps one first-failure slot for every batch
+ * call) reports the lowest failing index of the last such call, synchronising.
  *
- * dc_nyb_batch_bound = total_bytes + count: a buffer of len >= 1 bytes codes to at most len + 1
+ * dc_*_batch_bound = total_bytes + count: a buffer of len >= 1 bytes codes to at most len + 1
  * bytes (the LITERAL form), an empty one to the single byte ' '. Exact, and pure host arithmetic
- * (csrc/dc_nyb_batch_bound.h).
+ * (csrc/dc_nyb_batch_bound.h, csrc/dc_small_batch_bound.h).
  *
- * dc_nyb_compress_batch: buffer i = d_in[d_in_off[i] .. d_in_off[i+1]) (device u64, count + 1
- * entries; any alignment, any length, 0 too). Stream i is exactly what dc_nyb_compress writes for
- * that buffer alone (type byte 0xAF, the raw first byte, nybbles; ' ' and the raw bytes when the
- * nybble form is not shorter; ' ' alone for length 0), with the static or the adaptive (modify)
- * lists. The streams lie back to back in d_out: the call writes d_out_off[0] = 0 and
- * d_out_off[i+1] = d_out_off[i] + (length of stream i), count + 1 entries, always the true
- * lengths, so d_out_off[count] is the capacity the batch needs even when out_cap was too small.
+ * dc_*_compress_batch: buffer i = d_in[d_in_off[i] .. d_in_off[i+1]) (device u64, count + 1
+ * entries; any alignment, any length, 0 too). Stream i is exactly what the codec's single call
+ * writes for that buffer alone. The streams lie back to back in d_out: the call writes
+ * d_out_off[0] = 0 and d_out_off[i+1] = d_out_off[i] + (length of stream i), count + 1 entries,
+ * always the true lengths, so d_out_off[count] is the capacity the batch needs even when out_cap
+ * was too small.
  *   DC_E_ARG       the buffer's offsets decrease: it takes 0 output bytes, and nothing of it is
  *                  read or written
  *   DC_E_CAPACITY  d_out_off[i+1] > out_cap: nothing of it is written
  * Nothing is ever written at or past d_out + out_cap, and no byte of d_out that belongs to no
- * stream is written.
+ * good stream is written.
+ *
+ * dc_nyb_decompress_batch_async / dc_small_decompress_batch: stream i = d_in[d_in_off[i] ..
+ * d_in_off[i+1]) is decoded into d_out[d_out_off[i] .. d_out_off[i+1]), where the CALLER gives
+ * d_out_off (count + 1 entries): the format stores no length, so the length asked for must be the
+ * stream's. One launch.
+ *   DC_E_ARG       either offset pair decreases: nothing is read or written
+ *   DC_E_CAPACITY  d_out_off[i+1] > out_cap: nothing is written
+ *   DC_E_STREAM    the stream does not decode to exactly the asked length
+ * No byte outside a stream's own asked range is ever written.
+ *
+ * The status of entry i, in this order, from its two offset pairs alone (DC_E_STREAM is what the
+ * codec finds in an entry that passed): DC_E_ARG when d_in_off[i+1] < d_in_off[i], or, on decode,
+ * d_out_off[i+1] < d_out_off[i]; else DC_E_CAPACITY when d_out_off[i+1] > out_cap (on encode also
+ * when d_out_off[i+1] < d_out_off[i]: the call's own sum of the lengths wrapped 2^64). So an entry
+ * whose input pair decreases is DC_E_ARG even past the point where the capacity ran out. */
+
+/* ---- nybble batch v1: many buffers of their own lengths, one call each way -------------------
+ * The streams are the reference's own ("byte-stream batch v1" above has the calls' contract).
+ *
+ * dc_nyb_compress_batch: stream i is exactly what dc_nyb_compress writes for that buffer alone
+ * (type byte 0xAF, the raw first byte, nybbles; ' ' and the raw bytes when the nybble form is not
+ * shorter; ' ' alone for length 0), with the static or the adaptive (modify) lists.
  * Byte domain: for buffers of bytes 1..255 the streams are the reference's. Byte 0 is outside the
  * reference's domain (its API takes NUL-terminated strings), and the one-lane-per-stream kernels
  * keep their lists padded with zero bytes, which is not exact for a zero input byte: such input
@@ -615,17 +638,10 @@ int dc_nyb_decompress_batch(dc_ctx *ctx, const uint8_t *d_in, const uint64_t *d_
  * wave runs for as long as its longest buffer: batches of very unequal lengths are best sorted by
  * length (tools/nyb_batch_bench.py records the difference). There is no maximum buffer length.
  *
- * dc_nyb_decompress_batch_async: stream i = d_in[d_in_off[i] .. d_in_off[i+1]) is decoded into
- * d_out[d_out_off[i] .. d_out_off[i+1]), where the CALLER gives d_out_off (count + 1 entries): the
- * format stores no length, so the length asked for must be the stream's. The type dispatch is
- * dc_nyb_decompress_batch's (0xAF nybbles, ' ' raw, any other type byte copies the whole stream).
- * One launch.
- *   DC_E_ARG       either offset pair decreases: nothing is read or written
- *   DC_E_CAPACITY  d_out_off[i+1] > out_cap: nothing is written
- *   DC_E_STREAM    the stream does not decode to exactly the asked length
- * No byte outside a stream's own asked range is ever written. The contents of a FAILED stream's
- * own range are unspecified: there is no framing to verify before the walk, and a verify pass
- * (a second walk of every stream) is not worth its cost here. */
+ * dc_nyb_decompress_batch_async: the type dispatch is dc_nyb_decompress_batch's (0xAF nybbles, ' '
+ * raw, any other type byte copies the whole stream). The contents of a FAILED stream's own range
+ * are unspecified: there is no framing to verify before the walk, and a verify pass (a second walk
+ * of every stream) is not worth its cost here. */
 uint64_t dc_nyb_batch_bound(uint64_t total_bytes, uint64_t count);
 int dc_nyb_compress_batch(dc_ctx *ctx, const uint8_t *d_in, const uint64_t *d_in_off, uint64_t count, int modify,
                           uint8_t *d_out, uint64_t out_cap, uint64_t *d_out_off, int32_t *d_status);
@@ -669,34 +685,14 @@ int dc_small_compress(dc_ctx *ctx, const uint8_t *d_in, uint64_t n, uint8_t *d_o
 int dc_small_decompress(dc_ctx *ctx, const uint8_t *d_in, uint64_t m, uint8_t *d_out,
                         uint64_t *h_out_len);
 /* ---- small batch v1: many buffers of their own lengths, one call each way ---------------------
- * The format is nothing but the front-end's own streams back to back plus their offsets: no
- * header, no container. Both calls are asynchronous on the context's stream, make no host read,
- * and launch the same kernels for any count and any lengths, so a round trip can be enqueued or
- * captured (the first call at a larger count grows the context's 16 B of scratch per buffer).
- * count 0 returns DC_OK without a launch; count > DC_RANGES_MAX, a NULL context or (with
- * count > 0) any NULL pointer returns DC_E_ARG. A bad buffer never stops the others.
- * d_status[i] (i32, count entries) receives each buffer's outcome, and dc_huff_batch_status
- * (the context keeps one first-failure slot for every batch call) reports the lowest failing
- * index of the last such call, synchronising. DC_OPT_BATCH_GRID sizes the grids.
+ * The streams are the front-end's own ("byte-stream batch v1" above has the calls' contract).
+ * DC_OPT_BATCH_GRID sizes the grids.
  *
- * dc_small_batch_bound = total_bytes + count: a buffer of len >= 1 bytes codes to at most len + 1
- * bytes (the LITERAL form), an empty one to the single byte ' '. Exact, and pure host arithmetic
- * (csrc/dc_small_batch_bound.h).
- *
- * dc_small_compress_batch: buffer i = d_in[d_in_off[i] .. d_in_off[i+1]) (device u64, count + 1
- * entries; any alignment, any length, 0 too). Stream i is exactly what dc_small_compress writes
- * for that buffer alone. With P = the positions i >= 1, i + 1 < len, that hold ' ' before a..z:
- * for P >= 2 the pruned form (the type byte 8, the raw first byte, then every byte as itself but a
- * pair as the one byte 0x80 + letter: len + 1 - P bytes), else the LITERAL form (' ' and the
- * bytes), ' ' alone for length 0. All 256 byte values are in the domain, 0 included. The streams
- * lie back to back in d_out: the call writes d_out_off[0] = 0 and d_out_off[i+1] = d_out_off[i] +
- * (length of stream i), count + 1 entries, always the true lengths, so d_out_off[count] is the
- * capacity the batch needs even when out_cap was too small.
- *   DC_E_ARG       the buffer's offsets decrease: it takes 0 output bytes, and nothing of it is
- *                  read or written
- *   DC_E_CAPACITY  d_out_off[i+1] > out_cap: nothing of it is written
- * Nothing is ever written at or past d_out + out_cap, and no byte of d_out that belongs to no
- * good stream is written.
+ * dc_small_compress_batch: stream i is exactly what dc_small_compress writes for that buffer
+ * alone. With P = the positions i >= 1, i + 1 < len, that hold ' ' before a..z: for P >= 2 the
+ * pruned form (the type byte 8, the raw first byte, then every byte as itself but a pair as the
+ * one byte 0x80 + letter: len + 1 - P bytes), else the LITERAL form (' ' and the bytes), ' ' alone
+ * for length 0. All 256 byte values are in the domain, 0 included.
  * Cost: three launches, a count pass (P -> the stream's length), a scan and a write pass straight
  * to the final place (it knows the form from the length: len + 1 is LITERAL). One WAVE codes one
  * buffer, in tiles of 1 KiB, and takes buffers in a fixed stride: 64 unequal buffers do not wait
@@ -705,15 +701,10 @@ int dc_small_decompress(dc_ctx *ctx, const uint8_t *d_in, uint64_t m, uint8_t *d
  * difference). A buffer is never split between waves: buffers of many MiB belong in
  * dc_small_compress, which spreads one stream over the device. There is no maximum buffer length.
  *
- * dc_small_decompress_batch: stream i = d_in[d_in_off[i] .. d_in_off[i+1]) is decoded into
- * d_out[d_out_off[i] .. d_out_off[i+1]), where the CALLER gives d_out_off (count + 1 entries): the
- * format stores no length, so the length asked for must be the stream's. The type dispatch is
- * dc_small_decompress's: type 8 with m >= 2 bytes gives byte 1 raw, then ' ', b - 0x80 for every
- * later byte b >= 0x80 and b itself otherwise; ' ' gives the m - 1 bytes after it; an empty stream,
- * a lone type 8 and any other type byte give nothing (length 0). One launch.
- *   DC_E_ARG       either offset pair decreases: nothing is read or written
- *   DC_E_CAPACITY  d_out_off[i+1] > out_cap
- *   DC_E_STREAM    the stream does not decode to exactly the asked length
+ * dc_small_decompress_batch: the type dispatch is dc_small_decompress's: type 8 with m >= 2 bytes
+ * gives byte 1 raw, then ' ', b - 0x80 for every later byte b >= 0x80 and b itself otherwise; ' '
+ * gives the m - 1 bytes after it; an empty stream, a lone type 8 and any other type byte give
+ * nothing (length 0).
  * A stream with any status but DC_OK writes NO byte (the decoded length is a count over the
  * stream: the kernel counts first and writes only when it matches), and no byte outside a good
  * stream's own range is ever written. A pruned stream that holds a raw input byte >= 0x80 after

@@ -11,12 +11,11 @@ import numpy as np
 import pytest
 
 from oracle import oracle as orc
-from tests.test_nyb_batch_cpu import I_HIGH, I_RANDOM_100, STREAM_INPUTS, oracle_streams, pack_offsets
+from tests.stream_batch_checks import DC_E_ARG, DC_E_CAPACITY, DC_E_STREAM, FILL, _check_streams, _cum, _dev, pack_offsets
+from tests.test_nyb_batch_cpu import I_HIGH, I_RANDOM_100, STREAM_INPUTS, oracle_streams
 
 pytestmark = pytest.mark.gpu
 
-FILL = 0xA5
-DC_E_ARG, DC_E_CAPACITY, DC_E_STREAM = -1, -6, -7
 MODES = (False, True)
 
 
@@ -34,16 +33,6 @@ def codec(torch_cuda):
     return Codec(0)
 
 
-def _dev(torch, a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def _cum(streams):
-    off = np.zeros(len(streams) + 1, np.int64)
-    off[1:] = np.cumsum([len(s) for s in streams])
-    return off
-
-
 def _encode(torch, codec, x, off, modify, out_cap=None):
     """nyb_compress_batch into a 0xA5-filled buffer of bound + 48 bytes: host (out, out_off, status)."""
     count = len(off) - 1
@@ -51,23 +40,6 @@ def _encode(torch, codec, x, off, modify, out_cap=None):
     o, oo, st = codec.nyb_compress_batch(_dev(torch, x), _dev(torch, off), modify, out=out, out_cap=out_cap)
     assert o is out
     return out.cpu().numpy(), oo.cpu().numpy(), st.cpu().numpy()
-
-
-def _check_streams(h, oo, st, want, tag, bad=None):
-    """Every stream not in `bad` (index -> status) is the oracle's at its place; a bad one takes
-    the bytes want[i] says (b"" for DC_E_ARG) and writes none; all else keeps the prefill."""
-    bad = bad or {}
-    exp_off = _cum(want)
-    assert np.array_equal(oo, exp_off), tag + ("out_off",)
-    written = np.zeros(h.size, bool)
-    for i, s in enumerate(want):
-        if i in bad:
-            assert st[i] == bad[i], tag + (i, "status", int(st[i]))
-            continue
-        assert st[i] == 0, tag + (i, int(st[i]))
-        assert h[exp_off[i]: exp_off[i + 1]].tobytes() == s, tag + (i, "stream")
-        written[exp_off[i]: exp_off[i + 1]] = True
-    assert (h[~written] == FILL).all(), tag + ("bytes of no good stream written",)
 
 
 @pytest.fixture(scope="module")
@@ -315,3 +287,54 @@ def test_blocks_are_the_chunk_streams_of_the_container(torch_cuda, codec, modify
     h = o.cpu().numpy()
     assert np.array_equal(h[: c_off[-1]], payload[: c_off[-1]]) and payload.size == c_off[-1]
     assert (h[c_off[-1]:] == FILL).all()
+
+
+def _edge_input(K, nchunks):
+    """(nchunks - 1) K + 1 bytes, so the last chunk is a single byte: text in the even chunks,
+    bytes 1..127 in the odd ones (no zero byte), which do not pay as nybbles."""
+    from data_compression_amd import synth
+    n = (nchunks - 1) * K + 1
+    x = synth.english_like(n, seed=1000 * K + nchunks).copy()
+    rng = np.random.default_rng(K * 131 + nchunks)
+    for c in range(1, nchunks, 2):
+        lo, hi = c * K, min((c + 1) * K, n)
+        x[lo:hi] = rng.integers(1, 128, size=hi - lo, dtype=np.uint8)
+    return x
+
+
+@pytest.mark.parametrize("modify", MODES)
+@pytest.mark.parametrize("nchunks", (1, 63, 64, 65, 129))
+@pytest.mark.parametrize("K", (16, 17, 100, 300))
+def test_container_chunks_are_the_batch_streams_at_every_edge(torch_cuda, codec, K, nchunks, modify):
+    """The DCNK encoder (k_nyb_chunk_enc) and the batch encoder (nyb_lane_encode) hold the same walk
+    twice: at chunk sizes around a granule and a line, and at the wave's edges, every chunk of the
+    container is the oracle's stream of that chunk, the container is nyb_compress_blocks's streams
+    at its offsets, and it decodes to the input. From 63 chunks on, both forms occur, and a full
+    chunk is LITERAL: at K = 300 its slot is rewritten after whole lines have left."""
+    torch = torch_cuda
+    x = _edge_input(K, nchunks)
+    n = x.size
+    chunks = [x[c * K: (c + 1) * K].tobytes() for c in range(nchunks)]
+    assert len(chunks[-1]) == 1
+    want = [orc.nybble_compress(c, modify) for c in chunks]
+    forms = {(s[0], len(c) == K) for s, c in zip(want, chunks)}
+    if nchunks >= 63:
+        assert {f for f, _ in forms} == {0xAF, 0x20} and (0x20, True) in forms, (K, nchunks, modify)
+    else:
+        assert want == [b" " + chunks[0]]
+    xd = _dev(torch, x)
+    box = codec.nyb_compress_chunked(xd, modify, K)
+    h = box.cpu().numpy()
+    assert h[:4].tobytes() == b"DCNK" and int(h[24:32].view(np.uint64)[0]) == nchunks
+    c_off = h[32: 32 + 8 * (nchunks + 1)].view(np.uint64).astype(np.int64)
+    payload = h[32 + 8 * (nchunks + 1):]
+    assert np.array_equal(c_off, _cum(want)) and payload.size == c_off[-1], (K, nchunks, modify)
+    for c, s in enumerate(want):
+        assert payload[c_off[c]: c_off[c + 1]].tobytes() == s, (K, nchunks, modify, c)
+    out = torch.full((codec.nyb_batch_bound(n, nchunks) + 48,), FILL, dtype=torch.uint8, device="cuda")
+    o, oo, st = codec.nyb_compress_blocks(xd, K, modify, out=out)
+    assert codec.batch_status() == 0 and (st.cpu().numpy() == 0).all() and st.numel() == nchunks
+    assert np.array_equal(oo.cpu().numpy(), c_off)
+    b = o.cpu().numpy()
+    assert np.array_equal(b[: c_off[-1]], payload) and (b[c_off[-1]:] == FILL).all()
+    assert np.array_equal(codec.nyb_decompress_chunked(box).cpu().numpy(), x)

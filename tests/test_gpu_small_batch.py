@@ -12,13 +12,11 @@ import numpy as np
 import pytest
 
 from oracle import oracle as orc
-from tests.test_small_batch_cpu import (I_HIGH, I_HIGH_FIRST, I_RANDOM_100, LITERAL, PRUNED, SMALL_INPUTS, oracle_streams,
-                                        pack_offsets)
+from tests.stream_batch_checks import DC_E_ARG, DC_E_CAPACITY, DC_E_STREAM, FILL, _check_streams, _cum, _dev, pack_offsets
+from tests.test_small_batch_cpu import I_HIGH, I_HIGH_FIRST, I_RANDOM_100, LITERAL, PRUNED, SMALL_INPUTS, oracle_streams
 
 pytestmark = pytest.mark.gpu
 
-FILL = 0xA5
-DC_E_ARG, DC_E_CAPACITY, DC_E_STREAM = -1, -6, -7
 WAVES = 4   # SB_WAVES: buffers a workgroup takes per round
 
 
@@ -36,16 +34,6 @@ def codec(torch_cuda):
     return Codec(0)
 
 
-def _dev(torch, a):
-    return torch.from_numpy(np.array(a, copy=True)).cuda()   # (np.frombuffer arrays are read-only)
-
-
-def _cum(streams):
-    off = np.zeros(len(streams) + 1, np.int64)
-    off[1:] = np.cumsum([len(s) for s in streams])
-    return off
-
-
 def _encode(torch, codec, x, off, out_cap=None):
     """small_compress_batch into a 0xA5-filled buffer of bound + 48 bytes: host (out, out_off, status)."""
     count = len(off) - 1
@@ -53,23 +41,6 @@ def _encode(torch, codec, x, off, out_cap=None):
     o, oo, st = codec.small_compress_batch(_dev(torch, x), _dev(torch, off), out=out, out_cap=out_cap)
     assert o is out
     return out.cpu().numpy(), oo.cpu().numpy(), st.cpu().numpy()
-
-
-def _check_streams(h, oo, st, want, tag, bad=None):
-    """Every stream not in `bad` (index -> status) is the oracle's at its place; a bad one takes
-    the bytes want[i] says (b"" for DC_E_ARG) and writes none; all else keeps the prefill."""
-    bad = bad or {}
-    exp_off = _cum(want)
-    assert np.array_equal(oo, exp_off), tag + ("out_off",)
-    written = np.zeros(h.size, bool)
-    for i, s in enumerate(want):
-        if i in bad:
-            assert st[i] == bad[i], tag + (i, "status", int(st[i]))
-            continue
-        assert st[i] == 0, tag + (i, int(st[i]))
-        assert h[exp_off[i]: exp_off[i + 1]].tobytes() == s, tag + (i, "stream")
-        written[exp_off[i]: exp_off[i + 1]] = True
-    assert (h[~written] == FILL).all(), tag + ("bytes of no good stream written",)
 
 
 @pytest.fixture(scope="module")

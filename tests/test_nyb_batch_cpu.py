@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle as orc
+from tests.stream_batch_checks import pack_offsets
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DC_E_ARG = -1
@@ -34,13 +35,6 @@ def _inputs():
 
 STREAM_INPUTS = _inputs()
 I_RANDOM_100, I_RANDOM_3000, I_HIGH = 70, 71, 72   # their places in STREAM_INPUTS
-
-
-def pack_offsets(bufs):
-    """The buffers back to back (most offsets odd): (bytes, int64 offsets of count + 1)."""
-    off = np.zeros(len(bufs) + 1, np.int64)
-    off[1:] = np.cumsum([b.size for b in bufs])
-    return (np.concatenate(bufs) if bufs else np.zeros(0, np.uint8)), off
 
 
 @functools.lru_cache(maxsize=None)

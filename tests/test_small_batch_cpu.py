@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle as orc
+from tests.stream_batch_checks import pack_offsets
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DC_E_ARG = -1
@@ -42,13 +43,6 @@ def _inputs():
 SMALL_INPUTS = _inputs()
 I_EDGE, I_RANDOM_100, I_HAND = 80, 94, 95         # their places in SMALL_INPUTS
 I_ZERO, I_HIGH, I_HIGH_FIRST, I_ENDS_SPACE, I_BEGINS_A, I_TEXTS = 102, 103, 104, 105, 106, 107
-
-
-def pack_offsets(bufs):
-    """The buffers back to back (most offsets odd): (bytes, int64 offsets of count + 1)."""
-    off = np.zeros(len(bufs) + 1, np.int64)
-    off[1:] = np.cumsum([b.size for b in bufs])
-    return (np.concatenate(bufs) if bufs else np.zeros(0, np.uint8)), off
 
 
 @functools.lru_cache(maxsize=None)

@@ -46,6 +46,10 @@ elif a.stage in ("batch", "chunk_enc"):   # the one-lane-per-stream nybble paths
     nch = (x.numel() + 4095) // 4096
     offs = cont[32: 32 + 8 * (nch + 1)].view(torch.int64).clone()
     pay = cont[32 + 8 * (nch + 1):]
+elif a.stage in ("nyb_batch_v1", "small_batch_v1"):   # the batch calls on the same cut: 65536 buffers of 4 KiB
+    x = x[: 256 << 20]
+    boff = torch.arange(0, x.numel() + 1, 4096, dtype=torch.int64, device=dev)
+    bbuf = torch.empty(x.numel() + boff.numel(), dtype=torch.uint8, device=dev)   # the bound: total + count
 else:
     enc = c.encode(x, n_ary=a.nary, sync_syms=64)
 out = torch.empty_like(x)
@@ -67,6 +71,12 @@ def run():
         c.nyb_decompress_batch(pay, offs, True, out_cap=x.numel())
     elif a.stage == "chunk_enc":
         c.nyb_compress_chunked(x, True, 4096)
+    elif a.stage == "nyb_batch_v1":
+        o, oo, _ = c.nyb_compress_batch(x, boff, True, out=bbuf)
+        c.nyb_decompress_batch_into(o, oo, True, boff, out=out)
+    elif a.stage == "small_batch_v1":
+        o, oo, _ = c.small_compress_batch(x, boff, out=bbuf)
+        c.small_decompress_batch_into(o, oo, boff, out=out)
     elif a.stage == "hist":
         c.hist(x)
     else:
