@@ -19,11 +19,13 @@
 //                 and a byte tail
 // A segment's status goes to status[i]; the lowest failing (index, status) of the call is kept
 // in *first (atomicMin) for dc_huff_batch_status.
-// What a segment takes once its table is in LDS is here once, for this mode and for the shared-
-// table mode (dc_batch_shared_kernels.inc): hb_pack_seg (the whole of a pack), hb_decode_check and
-// hb_decode_body (the validation of a segment, and its chunk loop, commit and phased write) and
-// hb_decode_slow. The kernels differ in where the table comes from: k_hb_pack and k_hb_decode
-// build it per segment from lens (hb_canonical), the shared kernels copy it once per workgroup.
+// What a segment takes once its table is in LDS is here once, for this mode, for the shared-table
+// mode (dc_batch_shared_kernels.inc) and for the byte ranges of both (dc_batch_range_kernels.inc):
+// hb_pack_seg (the whole of a pack); hb_record_check (the tests of a segment's record) under
+// hb_decode_check and hb_range_check; hb_decode_body (the chunk loop, commit and phased write of an
+// HbSpan, a whole segment or with RANGE a byte range of one); hb_decode_slow. The kernels differ
+// in where the table comes from: k_hb_pack builds it per segment from lens (hb_canonical), k_hb_decode
+// and k_hb_decode_ranges likewise (hb_own_tables), the shared kernels copy it once per workgroup.
 
 #define HB_THREADS 256
 #define HB_UNIT 16                                   /* symbols per pack work unit (divides S)  */
@@ -332,7 +334,7 @@ __global__ __launch_bounds__(HB_THREADS) void k_hb_pack(const uint8_t *__restric
 #define HB_OIDX(pos) ((pos) + 4u * ((pos) >> 7))
 #define HB_STAGE_BYTES (DC_BATCH_SEG_MAX + 16 + 4 * (DC_BATCH_SEG_MAX / 128 + 1))
 
-// What hb_decode_check and hb_decode_body want of a decode kernel's LDS: lut, scan, bad, and in C
+// What hb_decode_body wants of a decode kernel's LDS: lut, scan, bad, and in C
 // the canonical arrays cnt / startv / starti / syms / mn / mx of hb_decode_slow.
 struct HbDecLds {
     __attribute__((aligned(16))) uint8_t out[HB_STAGE_BYTES];
@@ -342,6 +344,7 @@ struct HbDecLds {
     int bad;
 };
 
+// what every decode kernel takes of the batch, its output and the call
 struct HbDecArgs {
     int nary, w;
     uint32_t S;
@@ -354,7 +357,7 @@ struct HbDecArgs {
     const uint16_t *sync_len;
     uint64_t sync_cap;
     uint8_t *out;
-    const uint64_t *out_beg, *out_end;   // (the two may alias: d_out_off, d_out_off + 1)
+    const uint64_t *out_beg, *out_end;   // whole segments (the two may alias: d_out_off, d_out_off + 1); ranges: null
     uint64_t out_cap;
     int32_t *status;
     unsigned long long *first;
@@ -401,21 +404,48 @@ static __device__ __forceinline__ uint32_t hb_decode_slow(uint32_t win, uint32_t
     return 0;
 }
 
-// a segment that passed hb_decode_check
-struct HbSeg {
-    uint32_t len, md, sb, nch;   // output bytes (> 0), mode, bits, chunks
-    uint64_t po, pe, so;         // its payload bytes [po, pe), its first sync entry
-    uint8_t *dptr;               // where its output goes
+// What hb_decode_body decodes: a segment that passed hb_decode_check, or the byte range of one
+// that passed hb_range_check (dc_batch_range_kernels.inc).
+struct HbSpan {
+    uint64_t seg;            // the segment's number
+    uint32_t len, md, sb;    // its output bytes, mode and bits
+    uint64_t po, pe, so;     // its payload bytes [po, pe), its first sync entry
+    uint32_t c_lo, c_hi;     // the chunks decoded: all of them, or those a range touches
+    uint32_t first, count;   // the bytes [first, first + count) staged and written: all len, or a range (count > 0)
+    uint8_t *dptr;           // where they go
 };
+
+// The record of segment `seg` of len output bytes: its mode and bits, its payload bytes and its sync
+// entries against len, as both checks test them. Writes no status; with true, G is the whole
+// segment but for dptr. FILL_LATE: G is written only when the tests pass, else before their outcome
+// is used. Both give the same G to a caller that reads it only after true; which one the compiler
+// sees decides how it lays out the kernel around the call. k_hbs_decode takes true: it then
+// compiles to the instructions it had when segments and ranges had a body each. The other three
+// kernels take false: they measured 0.5 to 2 % slower with true
+// (profiles/batch_decode_span_forms.log, the late_fill runs).
+template <bool FILL_LATE>
+static __device__ __forceinline__ bool hb_record_check(const HbDecArgs &A, uint64_t seg, uint32_t len, HbSpan &G)
+{
+    const uint32_t S = A.S, slog = (uint32_t)__builtin_ctz(S);
+    const uint32_t md = A.mode[seg], sb = A.bits[seg];
+    const uint64_t po = A.pay_off[seg], pe = A.pay_off[seg + 1], so = A.sync_off[seg], se = A.sync_off[seg + 1];
+    const uint32_t nch = (len + S - 1) >> slog;
+    bool ok = md <= 1u && sb <= 8u * len && (md == 1u || sb == 8u * len);
+    ok = ok && pe >= po && pe <= A.payload_cap && (po & 15u) == 0 && pe - po == hb_pad16((sb + 7u) >> 3);
+    ok = ok && se >= so && se <= A.sync_cap && se - so == nch;
+    if (FILL_LATE && !ok) return false;
+    G = HbSpan{seg, len, md, sb, po, pe, so, 0u, nch, 0u, len, nullptr};
+    return ok;
+}
 
 // Segment i by the threads that call it (tt: the caller's index among them), a workgroup or a
 // wave: every test is uniform among them, and no barrier is reached. Validates the output range,
 // then the cap, then the stream's record, and writes the segment's status; with DC_OK it clears
 // *flag when the caller gives one (a workgroup's commit flag, see hb_decode_body). true: G is a
 // segment for hb_decode_body (false: it failed, or has 0 bytes).
-static __device__ __forceinline__ bool hb_decode_check(const HbDecArgs &A, uint64_t i, uint32_t tt, HbSeg &G, int *flag)
+template <bool FILL_LATE>
+static __device__ __forceinline__ bool hb_decode_check(const HbDecArgs &A, uint64_t i, uint32_t tt, HbSpan &G, int *flag)
 {
-    const uint32_t S = A.S, slog = (uint32_t)__builtin_ctz(S);
     const uint64_t oa = A.out_beg[i], ob = A.out_end[i];
     if (ob < oa || ob - oa > DC_BATCH_SEG_MAX) {
         if (tt == 0) hb_fail(A.status, A.first, i, DC_E_ARG);
@@ -425,14 +455,7 @@ static __device__ __forceinline__ bool hb_decode_check(const HbDecArgs &A, uint6
         if (tt == 0) hb_fail(A.status, A.first, i, DC_E_CAPACITY);
         return false;
     }
-    const uint32_t len = (uint32_t)(ob - oa);
-    const uint32_t md = A.mode[i], sb = A.bits[i];
-    const uint64_t po = A.pay_off[i], pe = A.pay_off[i + 1], so = A.sync_off[i], se = A.sync_off[i + 1];
-    const uint32_t nch = (len + S - 1) >> slog;
-    bool ok = md <= 1u && sb <= 8u * len && (md == 1u || sb == 8u * len);
-    ok = ok && pe >= po && pe <= A.payload_cap && (po & 15u) == 0 && pe - po == hb_pad16((sb + 7u) >> 3);
-    ok = ok && se >= so && se <= A.sync_cap && se - so == nch;
-    if (!ok) {
+    if (!hb_record_check<FILL_LATE>(A, i, (uint32_t)(ob - oa), G)) {
         if (tt == 0) hb_fail(A.status, A.first, i, DC_E_STREAM);
         return false;
     }
@@ -440,36 +463,55 @@ static __device__ __forceinline__ bool hb_decode_check(const HbDecArgs &A, uint6
         A.status[i] = DC_OK;
         if (flag) *flag = 0;
     }
-    G = HbSeg{len, md, sb, nch, po, pe, so, A.out + oa};
-    return len != 0;
+    G.dptr = A.out + oa;
+    return G.len != 0;
 }
 
-// The segment G (number i) staged at `stage`, by the NT threads that hb_decode_check ran on; for
-// a mode-1 segment L.lut and L.C hold its code. The whole workgroup (WAVE false: every barrier
-// below is reached by all of it, every test before one is uniform, and the caller has cleared
-// L.bad, the commit flag, after the barrier that ended the segment before), or one wave (WAVE
-// true: wave-uniform tests, no workgroup barrier, L.bad not used).
-template <bool WAVE, class Lds>
+// The span G (segment or range number i: where its status goes) staged at `stage`, by the NT
+// threads that its check ran on; for a mode-1 segment L.lut and L.C hold its code. The whole
+// workgroup (WAVE false: every barrier below is reached by all of it, every test before one is
+// uniform, and the caller has cleared L.bad, the commit flag, after the barrier that ended the span
+// before), or one wave (WAVE true: wave-uniform tests, no workgroup barrier, L.bad not used).
+// Byte k of the span is staged at HB_OIDX(phase + k).
+// RANGE false, a whole segment (c_lo, first = 0, count = len; status DC_OK by hb_decode_check):
+// every symbol is staged, and the chunk lengths must sum to bits. RANGE true, a byte range: the
+// u16 entries before c_lo are summed for its bit position (strided reads, a wave or workgroup
+// reduce), every touched chunk is decoded whole and checked to take exactly its bits, only the
+// symbols of [first, first + count) are staged, the last touched chunk must end within bits, and
+// DC_OK is written at the commit.
+template <bool WAVE, bool RANGE, class Lds>
 static __device__ __forceinline__ void hb_decode_body(Lds &L, uint8_t *stage, const HbDecArgs &A, uint64_t i, uint32_t tt,
-                                                      const HbSeg &G)
+                                                      const HbSpan &G)
 {
     constexpr uint32_t NT = WAVE ? 64u : (uint32_t)HB_THREADS;
     const uint32_t S = A.S, slog = (uint32_t)__builtin_ctz(S);
-    const uint32_t len = G.len, md = G.md, nch = G.nch;
+    const uint32_t md = G.md, c_lo = RANGE ? G.c_lo : 0u, c_hi = G.c_hi;
+    const uint32_t lo = RANGE ? G.first : 0u, n = RANGE ? G.count : G.len, hi = lo + n;
     uint8_t *const dptr = G.dptr;
     const uint32_t phase = (uint32_t)(uintptr_t)dptr & 15u;
     const uint8_t *const pay = A.payload + G.po;
-    if (md == 0)
-        for (uint32_t k = tt; k < len; k += NT) stage[HB_OIDX(phase + k)] = pay[k];
-    // chunk c by thread c % NT, NT chunks at a time: their bit lengths scanned, then decoded
+    const uint16_t *const sl = A.sync_len + G.so;
+    if (md == 0)   // (lo + k < len <= bits / 8: inside the payload)
+        for (uint32_t k = tt; k < n; k += NT) stage[HB_OIDX(phase + k)] = pay[lo + k];
+    uint32_t base = 0;
+    if (RANGE) {   // the bit position of chunk c_lo: the entries before it (<= 4096 of <= 65535 each)
+        uint32_t before = 0;
+#pragma unroll 4
+        for (uint32_t c = tt; c < c_lo; c += NT) before += sl[c];
+        if (WAVE) {
+            base = (uint32_t)__builtin_amdgcn_readlane((int)wave_scan_incl(before), 63);
+        } else {
+            wg_scan_excl_u32(before, L.scan, &base);
+        }
+    }
+    // chunk c by thread (c - c_lo) % NT, NT chunks at a time: their bit lengths scanned, then decoded
     const uint32_t nw = (uint32_t)(G.pe - G.po) / 4;
     const uint32_t *const pw = reinterpret_cast<const uint32_t *>(pay);
 #define HB_WORD(k) ((k) < nw ? bswap32(pw[k]) : 0u)
-    uint32_t base = 0;
     int bad = 0;
-    for (uint32_t c0 = 0; c0 < nch; c0 += NT) {
+    for (uint32_t c0 = c_lo; c0 < c_hi; c0 += NT) {
         const uint32_t c = c0 + tt;
-        const uint32_t clen = c < nch ? A.sync_len[G.so + c] : 0u;
+        const uint32_t clen = c < c_hi ? sl[c] : 0u;
         uint32_t tot, pos;
         if (WAVE) {   // (all 64 lanes are here: the loop's bounds are wave-uniform)
             const uint32_t incl = wave_scan_incl(clen);
@@ -479,9 +521,9 @@ static __device__ __forceinline__ void hb_decode_body(Lds &L, uint8_t *stage, co
             pos = base + wg_scan_excl_u32(clen, L.scan, &tot);
         }
         base += tot;
-        if (c >= nch || bad) continue;
+        if (c >= c_hi || bad) continue;
         const uint32_t sym0 = c << slog;
-        const uint32_t cnt = min(S, len - sym0);
+        const uint32_t cnt = min(S, G.len - sym0);
         if (md == 0) {   // stored: 8 bits a symbol
             bad |= clen != 8u * cnt;
             continue;
@@ -492,7 +534,7 @@ static __device__ __forceinline__ void hb_decode_body(Lds &L, uint8_t *stage, co
         int wbits = 64 - (int)sh;
         k += 2;
         uint32_t used = 0;
-        const uint32_t row = phase + sym0;
+        const uint32_t row = phase + sym0 - lo;   // (a range: only used where sym0 + j >= lo)
         for (uint32_t j = 0; j < cnt; ++j) {
             if (wbits < 32) {
                 win |= (uint64_t)HB_WORD(k) << (32 - wbits);
@@ -505,7 +547,8 @@ static __device__ __forceinline__ void hb_decode_body(Lds &L, uint8_t *stage, co
                 nb = hb_decode_slow((uint32_t)(win >> 32), HB_LUT_BITS + 1u, 32u, L.C, A.nary, A.w, sym);
                 if (!nb || sym >= 256u) { bad = 1; break; }   // no code, or the code of no byte (a dc_dtable's symbol >= 256)
             }
-            stage[HB_OIDX(row + j)] = (uint8_t)sym;
+            // (a range: only its first and last touched chunk hold symbols outside it)
+            if (!RANGE || (sym0 + j >= lo && sym0 + j < hi)) stage[HB_OIDX(row + j)] = (uint8_t)sym;
             win <<= nb;
             wbits -= (int)nb;
             used += nb;
@@ -513,63 +556,63 @@ static __device__ __forceinline__ void hb_decode_body(Lds &L, uint8_t *stage, co
         if (used != clen) bad = 1;
     }
 #undef HB_WORD
-    bool fail;   // (base: the chunk lengths must sum to bits)
+    // base: a segment's chunk lengths must sum to bits; a range's last touched chunk must end within them
+    bool fail;   // (the test is written in each branch: hoisted into one bool before them, k_hbs_decode
+                 // no longer compiles to the instructions it had, see hb_record_check)
     if (WAVE) {
         __builtin_amdgcn_wave_barrier();   // the stage is read by other lanes than wrote it
-        fail = __any(bad || base != G.sb);
+        fail = __any(bad || (RANGE ? base > G.sb : base != G.sb));
     } else {
-        if (bad || base != G.sb) L.bad = 1;
+        if (bad || (RANGE ? base > G.sb : base != G.sb)) L.bad = 1;
         __syncthreads();
         fail = L.bad != 0;
     }
-    if (fail) {   // nothing of a corrupt segment is written
+    if (fail) {   // nothing of a corrupt segment, or of a range with a corrupt chunk, is written
         if (tt == 0) hb_fail(A.status, A.first, i, DC_E_STREAM);
         return;
     }
+    if (RANGE && tt == 0) A.status[i] = DC_OK;
     // the stage has the destination's 16-B phase: a byte head, aligned 16-B pieces, a byte tail
-    const uint32_t head = min((16u - phase) & 15u, len);
+    const uint32_t head = min((16u - phase) & 15u, n);
     if (tt < head) dptr[tt] = stage[HB_OIDX(phase + tt)];
-    const uint32_t nbody = (len - head) >> 4;
+    const uint32_t nbody = (n - head) >> 4;
     for (uint32_t v = tt; v < nbody; v += NT) {   // (a piece never crosses a pad: 16 divides 128)
         const uint32_t *const q = reinterpret_cast<const uint32_t *>(stage + HB_OIDX(phase + head + 16 * v));
         *reinterpret_cast<uint4 *>(dptr + head + 16 * v) = make_uint4(q[0], q[1], q[2], q[3]);
     }
     const uint32_t tail = head + 16 * nbody + tt;
-    if (tail < len) dptr[tail] = stage[HB_OIDX(phase + tail)];
+    if (tail < n) dptr[tail] = stage[HB_OIDX(phase + tail)];
 }
 
-__global__ __launch_bounds__(HB_THREADS) void k_hb_decode(uint64_t count, int nary, int w, uint32_t S,
-                                                          const uint8_t *__restrict__ lens, const uint8_t *__restrict__ mode,
-                                                          const uint32_t *__restrict__ bits, const uint64_t *__restrict__ pay_off,
-                                                          const uint8_t *__restrict__ payload, uint64_t payload_cap,
-                                                          const uint64_t *__restrict__ sync_off,
-                                                          const uint16_t *__restrict__ sync_len, uint64_t sync_cap,
-                                                          uint8_t *__restrict__ out, const uint64_t *out_beg, const uint64_t *out_end,
-                                                          uint64_t out_cap, int32_t *__restrict__ status,
-                                                          unsigned long long *__restrict__ first)
+// The code of a lens record in L, by the whole workgroup (t: threadIdx.x): the canonical arrays,
+// then the 12-bit table; ends with a barrier. false: the lengths are no code (L.C.bad stays set,
+// no table is filled).
+static __device__ __forceinline__ bool hb_own_tables(HbDecLds &L, const uint8_t *__restrict__ lens, int nary, int w, int t)
+{
+    hb_canonical(L.C, lens, nary, w);
+    if (L.C.bad) return false;   // (uniform: read after hb_canonical's barrier)
+    for (uint32_t e = t; e < (1u << HB_LUT_BITS); e += HB_THREADS) {
+        uint32_t sym = 0;
+        const uint32_t nb = hb_decode_slow(e << (32 - HB_LUT_BITS), 1u, HB_LUT_BITS, L.C, nary, w, sym);
+        L.lut[e] = (uint16_t)(nb ? (sym | (nb << 8)) : 0u);
+    }
+    __syncthreads();
+    return true;
+}
+
+__global__ __launch_bounds__(HB_THREADS) void k_hb_decode(HbDecArgs A, uint64_t count, const uint8_t *__restrict__ lens)
 {
     __shared__ HbDecLds L;
     const int t = threadIdx.x;
-    const HbDecArgs A{nary, w, S, mode, bits, pay_off, payload, payload_cap, sync_off, sync_len, sync_cap,
-                      out, out_beg, out_end, out_cap, status, first};
     for (uint64_t i = blockIdx.x; i < count; i += gridDim.x) {
         __syncthreads();   // the LDS of the segment before
-        HbSeg G;
-        if (!hb_decode_check(A, i, (uint32_t)t, G, &L.bad)) continue;   // (uniform, as every test below)
-        if (G.md == 1u) {   // the table only now: a segment with a bad range or record has its status already
-            hb_canonical(L.C, lens + i * 256, nary, w);
-            if (L.C.bad) {   // (read after hb_canonical's barrier)
-                if (t == 0) hb_fail(status, first, i, DC_E_STREAM);
-                continue;
-            }
-            for (uint32_t e = t; e < (1u << HB_LUT_BITS); e += HB_THREADS) {
-                uint32_t sym = 0;
-                const uint32_t nb = hb_decode_slow(e << (32 - HB_LUT_BITS), 1u, HB_LUT_BITS, L.C, nary, w, sym);
-                L.lut[e] = (uint16_t)(nb ? (sym | (nb << 8)) : 0u);
-            }
-            __syncthreads();
+        HbSpan G;
+        if (!hb_decode_check<false>(A, i, (uint32_t)t, G, &L.bad)) continue;   // (uniform, as every test below)
+        // the table only now: a segment with a bad range or record has its status already
+        if (G.md == 1u && !hb_own_tables(L, lens + i * 256, A.nary, A.w, t)) {
+            if (t == 0) hb_fail(A.status, A.first, i, DC_E_STREAM);
+            continue;
         }
-        hb_decode_body<false>(L, L.out, A, i, (uint32_t)t, G);
+        hb_decode_body<false, false>(L, L.out, A, i, (uint32_t)t, G);
     }
 }
-

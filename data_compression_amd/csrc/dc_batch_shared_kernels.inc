@@ -4,7 +4,8 @@
 // so no work of a segment is proportional to the table: a persistent workgroup copies what it
 // needs of the table into LDS once, before its segment loop. Only what is particular to this
 // mode is here: what a segment takes once the table is in LDS (hb_pack_seg, hb_decode_check,
-// hb_decode_body, hb_decode_slow) is in dc_batch_kernels.inc, the same code as the own-table mode.
+// hb_decode_body, hb_decode_slow) is in dc_batch_kernels.inc, the same code as the own-table mode
+// and as the byte ranges of either (dc_batch_range_kernels.inc, which calls hbs_tables_load).
 //   k_hbs_plan    nbits[256] in LDS; per segment the sum of nb[byte] and whether a byte has no
 //                 code (no histogram, no table build): mode, bits, and the payload bytes and
 //                 sync entries for the scans
@@ -139,7 +140,7 @@ struct HbsCanon {
     int mn, mx;
 };
 
-struct HbsDecLds {   // (the members hb_decode_check and hb_decode_body use, as HbDecLds)
+struct HbsDecLds {   // (the members hb_decode_body uses, as HbDecLds)
     __attribute__((aligned(16))) uint8_t out[HB_STAGE_BYTES];
     uint16_t lut[1 << HB_LUT_BITS];   // next 12 bits -> sym | bits << 8; 0: longer, or no code
     HbsCanon C;
@@ -194,12 +195,15 @@ static_assert(4u * HBS_WAVE_STAGE <= sizeof(HbsDecLds::out) && HBS_WAVE_STAGE % 
 template <bool WAVE>
 static __device__ __forceinline__ void hbs_decode_seg(HbsDecLds &L, uint8_t *stage, const HbDecArgs &A, uint64_t i, uint32_t tt)
 {
-    HbSeg G;
-    if (!hb_decode_check(A, i, tt, G, nullptr)) return;
+    HbSpan G;
+    if (!hb_decode_check<true>(A, i, tt, G, nullptr)) return;   // (true: see hb_record_check)
     if (!WAVE && tt == 0) L.bad = 0;
-    hb_decode_body<WAVE>(L, stage, A, i, tt, G);
+    hb_decode_body<WAVE, false>(L, stage, A, i, tt, G);
 }
 
+// (The long parameter list, not HbDecArgs by value as k_hb_decode and k_hbs_decode_ranges take it:
+// the struct's pointers are not __restrict__, and with it this kernel decodes 64 KiB segments 4.9 %
+// and 4 KiB segments 1.4 % slower, profiles/batch_decode_span.log, the struct runs.)
 __global__ __launch_bounds__(HB_THREADS) void k_hbs_decode(uint64_t count, int nary, int w, uint32_t S,
                                                            const dc_dtable *__restrict__ T, const uint8_t *__restrict__ mode,
                                                            const uint32_t *__restrict__ bits, const uint64_t *__restrict__ pay_off,
@@ -213,22 +217,22 @@ __global__ __launch_bounds__(HB_THREADS) void k_hbs_decode(uint64_t count, int n
     __shared__ HbsDecLds L;
     const int t = threadIdx.x;
     const uint32_t lane = (uint32_t)t & 63u, wave = (uint32_t)t >> 6;
-    const bool tok = hbs_table_ok(T, nary);
-    if (tok) hbs_tables_load(L, T, t, lane, wave);   // (uniform) the decode tables, once for every segment of this workgroup
     const HbDecArgs A{nary, w, S, mode, bits, pay_off, payload, payload_cap, sync_off, sync_len, sync_cap,
                       out, out_beg, out_end, out_cap, status, first};
+    const bool tok = hbs_table_ok(T, A.nary);
+    if (tok) hbs_tables_load(L, T, t, lane, wave);   // (uniform) the decode tables, once for every segment of this workgroup
     const uint64_t groups = (count + 3) / 4;
     for (uint64_t g = blockIdx.x; g < groups; g += gridDim.x) {
         __syncthreads();   // the LDS of the group before (the first time: the tables)
         const uint64_t i0 = 4 * g;
         const uint32_t nseg = (uint32_t)min((uint64_t)4, count - i0);
         if (!tok) {
-            if ((uint32_t)t < nseg) hb_fail(status, first, i0 + (uint32_t)t, DC_E_ARG);
+            if ((uint32_t)t < nseg) hb_fail(A.status, A.first, i0 + (uint32_t)t, DC_E_ARG);
             continue;
         }
         bool shortg = true;   // (workgroup-uniform; a range that ends before it starts fails on either path)
         for (uint32_t s = 0; s < nseg; ++s) {
-            const uint64_t oa = out_beg[i0 + s], ob = out_end[i0 + s];
+            const uint64_t oa = A.out_beg[i0 + s], ob = A.out_end[i0 + s];
             shortg = shortg && !(ob > oa && ob - oa > HBS_WAVE_SEG);
         }
         if (shortg) {

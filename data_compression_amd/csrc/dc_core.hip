@@ -7371,20 +7371,54 @@ static uint64_t hbatch_grid(const dc_ctx *c, uint64_t work, uint64_t cap)
     return work < cap ? work : cap;
 }
 
+// What the two encodes begin with: 1 (nothing to do), 0 with d_hb sized and the first-failure slot
+// turned over, or an error.
+static int hbatch_encode_begin(dc_ctx *c, const dc_hbatch *b, bool need_lens, const uint64_t *d_in_off, uint64_t count,
+                               unsigned long long **first)
+{
+    if (const int r = hbatch_args(c, b, need_lens)) return r;
+    if (b->count != count) return DC_E_ARG;
+    if (count == 0) return 1;
+    if (!d_in_off || count > DC_RANGES_MAX) return DC_E_ARG;
+    return hbatch_begin(c, count, first);
+}
+
+// between an encode's plan and its pack: pay_off and sync_off from the plan's per-segment sizes
+static int hbatch_scans(dc_ctx *c, const dc_hbatch *b, const uint64_t *psize, const uint64_t *nch)
+{
+    LAUNCH(c, "hb_scan_pay", k_scan_u64, 1, 1024, psize, b->count, b->d_pay_off);
+    LAUNCH(c, "hb_scan_sync", k_scan_u64, 1, 1024, nch, b->count, b->d_sync_off);
+    return DC_OK;
+}
+
+// What the two whole-segment decodes begin with: as hbatch_encode_begin.
+static int hbatch_decode_begin(dc_ctx *c, const dc_hbatch *b, bool need_lens, const uint8_t *d_out, const uint64_t *d_out_beg,
+                               const uint64_t *d_out_end, uint64_t out_cap, unsigned long long **first)
+{
+    if (const int r = hbatch_args(c, b, need_lens)) return r;
+    if (b->count == 0) return 1;
+    if (!d_out_beg || !d_out_end || (!d_out && out_cap) || b->count > DC_RANGES_MAX) return DC_E_ARG;
+    return hbatch_begin(c, b->count, first);
+}
+
+// what every decode kernel takes (HbDecArgs): the batch, where the output goes and the statuses
+static HbDecArgs hbatch_dec_args(const dc_hbatch *b, uint8_t *d_out, const uint64_t *d_out_beg, const uint64_t *d_out_end,
+                                 uint64_t out_cap, int32_t *d_status, unsigned long long *first)
+{
+    return HbDecArgs{(int)b->n_ary, hbatch_w(b->n_ary), b->sync_syms, b->d_mode, b->d_bits, b->d_pay_off, b->d_payload,
+                     b->payload_cap, b->d_sync_off, b->d_sync_len, b->sync_cap, d_out, d_out_beg, d_out_end, out_cap,
+                     d_status, first};
+}
+
 int dc_huff_encode_batch(dc_ctx *c, const uint8_t *d_in, const uint64_t *d_in_off, uint64_t count, const dc_hbatch *b)
 {
-    if (const int r = hbatch_args(c, b, true)) return r;
-    if (b->count != count) return DC_E_ARG;
-    if (count == 0) return DC_OK;
-    if (!d_in_off || count > DC_RANGES_MAX) return DC_E_ARG;
     unsigned long long *first;
-    if (const int r = hbatch_begin(c, count, &first)) return r;
+    if (const int r = hbatch_encode_begin(c, b, true, d_in_off, count, &first)) return r > 0 ? DC_OK : r;
     uint64_t *const psize = c->d_hb + 2, *const nch = c->d_hb + 2 + count;
     const uint64_t g3 = hbatch_grid(c, count, 768), g2 = hbatch_grid(c, count, 512);   // LDS-bound: 3 and 2 per CU
     LAUNCH(c, "hb_plan", k_hb_plan, g3, HB_THREADS, d_in, d_in_off, count, (int)b->n_ary, b->sync_syms, b->d_lens, b->d_mode,
            b->d_bits, psize, nch, b->d_status, first);
-    LAUNCH(c, "hb_scan_pay", k_scan_u64, 1, 1024, (const uint64_t *)psize, count, b->d_pay_off);
-    LAUNCH(c, "hb_scan_sync", k_scan_u64, 1, 1024, (const uint64_t *)nch, count, b->d_sync_off);
+    if (const int r = hbatch_scans(c, b, psize, nch)) return r;
     LAUNCH(c, "hb_pack", k_hb_pack, g2, HB_THREADS, d_in, d_in_off, count, (int)b->n_ary, hbatch_w(b->n_ary), b->sync_syms,
            (const uint8_t *)b->d_lens, (const uint8_t *)b->d_mode, (const uint64_t *)b->d_pay_off, b->d_payload,
            b->payload_cap, (const uint64_t *)b->d_sync_off, b->d_sync_len, b->sync_cap, b->d_status, first);
@@ -7394,17 +7428,11 @@ int dc_huff_encode_batch(dc_ctx *c, const uint8_t *d_in, const uint64_t *d_in_of
 int dc_huff_decode_batch_scatter(dc_ctx *c, const dc_hbatch *b, uint8_t *d_out, const uint64_t *d_out_beg,
                                  const uint64_t *d_out_end, uint64_t out_cap)
 {
-    if (const int r = hbatch_args(c, b, true)) return r;
-    const uint64_t count = b->count;
-    if (count == 0) return DC_OK;
-    if (!d_out_beg || !d_out_end || (!d_out && out_cap) || count > DC_RANGES_MAX) return DC_E_ARG;
     unsigned long long *first;
-    if (const int r = hbatch_begin(c, count, &first)) return r;
-    const uint64_t g2 = hbatch_grid(c, count, 512);
-    LAUNCH(c, "hb_decode", k_hb_decode, g2, HB_THREADS, count, (int)b->n_ary, hbatch_w(b->n_ary), b->sync_syms,
-           (const uint8_t *)b->d_lens, (const uint8_t *)b->d_mode, (const uint32_t *)b->d_bits,
-           (const uint64_t *)b->d_pay_off, (const uint8_t *)b->d_payload, b->payload_cap, (const uint64_t *)b->d_sync_off,
-           (const uint16_t *)b->d_sync_len, b->sync_cap, d_out, d_out_beg, d_out_end, out_cap, b->d_status, first);
+    if (const int r = hbatch_decode_begin(c, b, true, d_out, d_out_beg, d_out_end, out_cap, &first)) return r > 0 ? DC_OK : r;
+    const uint64_t g2 = hbatch_grid(c, b->count, 512);
+    LAUNCH(c, "hb_decode", k_hb_decode, g2, HB_THREADS, hbatch_dec_args(b, d_out, d_out_beg, d_out_end, out_cap, b->d_status, first),
+           b->count, (const uint8_t *)b->d_lens);
     return DC_OK;
 }
 
@@ -7419,19 +7447,14 @@ int dc_huff_encode_batch_shared(dc_ctx *c, const uint8_t *d_in, const uint64_t *
                                 const dc_dtable *d_table, const dc_hbatch *b)
 {
     if (!d_table) return DC_E_ARG;
-    if (const int r = hbatch_args(c, b, false)) return r;
-    if (b->count != count) return DC_E_ARG;
-    if (count == 0) return DC_OK;
-    if (!d_in_off || count > DC_RANGES_MAX) return DC_E_ARG;
     unsigned long long *first;
-    if (const int r = hbatch_begin(c, count, &first)) return r;
+    if (const int r = hbatch_encode_begin(c, b, false, d_in_off, count, &first)) return r > 0 ? DC_OK : r;
     uint64_t *const psize = c->d_hb + 2, *const nch = c->d_hb + 2 + count;
     // the plan's LDS is 288 B (4 workgroups a CU), the pack's stage allows 2
     const uint64_t g4 = hbatch_grid(c, count, 1024), g2 = hbatch_grid(c, count, 512);
     LAUNCH(c, "hbs_plan", k_hbs_plan, g4, HB_THREADS, d_in, d_in_off, count, (int)b->n_ary, b->sync_syms, d_table, b->d_mode,
            b->d_bits, psize, nch, b->d_status, first);
-    LAUNCH(c, "hb_scan_pay", k_scan_u64, 1, 1024, (const uint64_t *)psize, count, b->d_pay_off);
-    LAUNCH(c, "hb_scan_sync", k_scan_u64, 1, 1024, (const uint64_t *)nch, count, b->d_sync_off);
+    if (const int r = hbatch_scans(c, b, psize, nch)) return r;
     LAUNCH(c, "hbs_pack", k_hbs_pack, g2, HB_THREADS, d_in, d_in_off, count, b->sync_syms, d_table, (const uint8_t *)b->d_mode,
            (const uint64_t *)b->d_pay_off, b->d_payload, b->payload_cap, (const uint64_t *)b->d_sync_off, b->d_sync_len,
            b->sync_cap, b->d_status, first);
@@ -7442,17 +7465,12 @@ int dc_huff_decode_batch_shared_scatter(dc_ctx *c, const dc_hbatch *b, const dc_
                                         const uint64_t *d_out_beg, const uint64_t *d_out_end, uint64_t out_cap)
 {
     if (!d_table) return DC_E_ARG;
-    if (const int r = hbatch_args(c, b, false)) return r;
-    const uint64_t count = b->count;
-    if (count == 0) return DC_OK;
-    if (!d_out_beg || !d_out_end || (!d_out && out_cap) || count > DC_RANGES_MAX) return DC_E_ARG;
     unsigned long long *first;
-    if (const int r = hbatch_begin(c, count, &first)) return r;
-    const uint64_t g2 = hbatch_grid(c, (count + 3) / 4, 512);   // a workgroup takes four segments at a time
-    LAUNCH(c, "hbs_decode", k_hbs_decode, g2, HB_THREADS, count, (int)b->n_ary, hbatch_w(b->n_ary), b->sync_syms, d_table,
-           (const uint8_t *)b->d_mode, (const uint32_t *)b->d_bits, (const uint64_t *)b->d_pay_off,
-           (const uint8_t *)b->d_payload, b->payload_cap, (const uint64_t *)b->d_sync_off, (const uint16_t *)b->d_sync_len,
-           b->sync_cap, d_out, d_out_beg, d_out_end, out_cap, b->d_status, first);
+    if (const int r = hbatch_decode_begin(c, b, false, d_out, d_out_beg, d_out_end, out_cap, &first)) return r > 0 ? DC_OK : r;
+    const uint64_t g2 = hbatch_grid(c, (b->count + 3) / 4, 512);   // a workgroup takes four segments at a time
+    const HbDecArgs A = hbatch_dec_args(b, d_out, d_out_beg, d_out_end, out_cap, b->d_status, first);
+    LAUNCH(c, "hbs_decode", k_hbs_decode, g2, HB_THREADS, b->count, A.nary, A.w, A.S, d_table, A.mode, A.bits, A.pay_off, A.payload,
+           A.payload_cap, A.sync_off, A.sync_len, A.sync_cap, A.out, A.out_beg, A.out_end, A.out_cap, A.status, A.first);
     return DC_OK;
 }
 
@@ -7478,33 +7496,33 @@ int dc_huff_batch_range_args(uint64_t seg_beg, uint64_t seg_end, uint64_t first,
     return dc_batch_range_args(len, first, count, out_off, out_cap);
 }
 
-// byte ranges of segments (dc_batch_range_kernels.inc). What both calls begin with, after
-// hbatch_args: 1 (nothing to do), 0 with the first-failure slot turned over, or an error.
-static int hbatch_ranges_begin(dc_ctx *c, const uint64_t *d_seg_off, const uint64_t *d_seg, const uint64_t *d_first,
-                               const uint64_t *d_count, const uint64_t *d_out_off, uint64_t nranges, const uint8_t *d_out,
-                               uint64_t out_cap, const int32_t *d_rstatus, unsigned long long **first)
+// byte ranges of segments (dc_batch_range_kernels.inc). What both calls begin with: as
+// hbatch_encode_begin (the slot alone: no plan arrays).
+static int hbatch_ranges_begin(dc_ctx *c, const dc_hbatch *b, bool need_lens, const uint64_t *d_seg_off, const uint64_t *d_seg,
+                               const uint64_t *d_first, const uint64_t *d_count, const uint64_t *d_out_off, uint64_t nranges,
+                               const uint8_t *d_out, uint64_t out_cap, const int32_t *d_rstatus, unsigned long long **first)
 {
+    if (const int r = hbatch_args(c, b, need_lens)) return r;
     if (nranges == 0) return 1;
     if (!d_seg_off || !d_seg || !d_first || !d_count || !d_out_off || !d_rstatus || (!d_out && out_cap)) return DC_E_ARG;
     if (nranges > DC_RANGES_MAX) return DC_E_ARG;
-    return hbatch_begin(c, 0, first);   // (the slot alone: no plan arrays)
+    return hbatch_begin(c, 0, first);
 }
 
 int dc_huff_decode_batch_ranges(dc_ctx *c, const dc_hbatch *b, const uint64_t *d_seg_off, const uint64_t *d_seg,
                                 const uint64_t *d_first, const uint64_t *d_count, const uint64_t *d_out_off,
                                 uint64_t nranges, uint8_t *d_out, uint64_t out_cap, int32_t *d_rstatus)
 {
-    if (const int r = hbatch_args(c, b, true)) return r;
     unsigned long long *first;
-    if (const int r = hbatch_ranges_begin(c, d_seg_off, d_seg, d_first, d_count, d_out_off, nranges, d_out, out_cap, d_rstatus,
-                                          &first))
+    if (const int r = hbatch_ranges_begin(c, b, true, d_seg_off, d_seg, d_first, d_count, d_out_off, nranges, d_out, out_cap,
+                                          d_rstatus, &first))
         return r > 0 ? DC_OK : r;
     const HbRangeArgs R{d_seg_off, d_seg, d_first, d_count, d_out_off, b->count};
     const uint64_t g2 = hbatch_grid(c, nranges, 512);   // LDS-bound: 2 per CU
-    LAUNCH(c, "hb_decode_ranges", k_hb_decode_ranges, g2, HB_THREADS, R, nranges, (int)b->n_ary, hbatch_w(b->n_ary),
-           b->sync_syms, (const uint8_t *)b->d_lens, (const uint8_t *)b->d_mode, (const uint32_t *)b->d_bits,
-           (const uint64_t *)b->d_pay_off, (const uint8_t *)b->d_payload, b->payload_cap, (const uint64_t *)b->d_sync_off,
-           (const uint16_t *)b->d_sync_len, b->sync_cap, d_out, out_cap, d_rstatus, first);
+    const HbDecArgs A = hbatch_dec_args(b, d_out, nullptr, nullptr, out_cap, d_rstatus, first);
+    LAUNCH(c, "hb_decode_ranges", k_hb_decode_ranges, g2, HB_THREADS, R, nranges, A.nary, A.w, A.S, (const uint8_t *)b->d_lens,
+           A.mode, A.bits, A.pay_off, A.payload, A.payload_cap, A.sync_off, A.sync_len, A.sync_cap, A.out, A.out_cap, A.status,
+           A.first);
     return DC_OK;
 }
 
@@ -7514,17 +7532,14 @@ int dc_huff_decode_batch_shared_ranges(dc_ctx *c, const dc_hbatch *b, const dc_d
                                        int32_t *d_rstatus)
 {
     if (!d_table) return DC_E_ARG;
-    if (const int r = hbatch_args(c, b, false)) return r;
     unsigned long long *first;
-    if (const int r = hbatch_ranges_begin(c, d_seg_off, d_seg, d_first, d_count, d_out_off, nranges, d_out, out_cap, d_rstatus,
-                                          &first))
+    if (const int r = hbatch_ranges_begin(c, b, false, d_seg_off, d_seg, d_first, d_count, d_out_off, nranges, d_out, out_cap,
+                                          d_rstatus, &first))
         return r > 0 ? DC_OK : r;
     const HbRangeArgs R{d_seg_off, d_seg, d_first, d_count, d_out_off, b->count};
     const uint64_t g2 = hbatch_grid(c, (nranges + 3) / 4, 512);   // a workgroup takes four ranges at a time
-    LAUNCH(c, "hbs_decode_ranges", k_hbs_decode_ranges, g2, HB_THREADS, R, nranges, (int)b->n_ary, hbatch_w(b->n_ary),
-           b->sync_syms, d_table, (const uint8_t *)b->d_mode, (const uint32_t *)b->d_bits, (const uint64_t *)b->d_pay_off,
-           (const uint8_t *)b->d_payload, b->payload_cap, (const uint64_t *)b->d_sync_off, (const uint16_t *)b->d_sync_len,
-           b->sync_cap, d_out, out_cap, d_rstatus, first);
+    LAUNCH(c, "hbs_decode_ranges", k_hbs_decode_ranges, g2, HB_THREADS,
+           hbatch_dec_args(b, d_out, nullptr, nullptr, out_cap, d_rstatus, first), R, nranges, d_table);
     return DC_OK;
 }
 

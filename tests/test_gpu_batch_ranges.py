@@ -41,25 +41,30 @@ def _dev(torch, a):
 _uploaded = {}
 
 
+def _upload(torch, codec, mode, segs, exp, n_ary, S):
+    """The oracle batch `exp` of `segs` on the device, as the dict encode_batch returns. status is
+    prefilled with -99: a range call must leave it alone."""
+    x, off = pack_offsets(segs)
+    enc = {"count": len(segs), "n_ary": n_ary, "S": S, "offsets": _dev(torch, off), "total": x.size,
+           "lens": _dev(torch, exp["lens"]) if mode == "own" else None,
+           "mode": _dev(torch, exp["mode"]), "bits": _dev(torch, exp["bits"].astype(np.int32)),
+           "pay_off": _dev(torch, exp["pay_off"]), "payload": _dev(torch, exp["payload"]),
+           "sync_off": _dev(torch, exp["sync_off"]), "sync_len": _dev(torch, exp["sync_len"].view(np.int16)),
+           "status": torch.full((len(segs),), -99, dtype=torch.int32, device="cuda"),
+           "payload_cap": exp["payload"].size, "sync_cap": exp["sync_len"].size}
+    assert enc["payload"].data_ptr() % 16 == 0
+    if mode == "shared":
+        enc["table"] = codec.table_lengths(_dev(torch, text_table(n_ary)), n_ary)
+    return enc
+
+
 def _enc(torch, codec, mode, n_ary=2, S=64):
-    """The oracle's batch of SEGMENTS on the device, as the dict encode_batch returns (uploaded once
-    per case: the tests clone what they change). status is prefilled with -99: a range call must
-    leave it alone."""
+    """The oracle's batch of SEGMENTS on the device (uploaded once per case: the tests clone what
+    they change)."""
     key = (mode, n_ary, S)
     if key not in _uploaded:
         exp = oracle_batch(SEGMENTS, n_ary, S) if mode == "own" else oracle_text_batch(n_ary, S)
-        x, off = pack_offsets(SEGMENTS)
-        enc = {"count": len(SEGMENTS), "n_ary": n_ary, "S": S, "offsets": _dev(torch, off), "total": x.size,
-               "lens": _dev(torch, exp["lens"]) if mode == "own" else None,
-               "mode": _dev(torch, exp["mode"]), "bits": _dev(torch, exp["bits"].astype(np.int32)),
-               "pay_off": _dev(torch, exp["pay_off"]), "payload": _dev(torch, exp["payload"]),
-               "sync_off": _dev(torch, exp["sync_off"]), "sync_len": _dev(torch, exp["sync_len"].view(np.int16)),
-               "status": torch.full((len(SEGMENTS),), -99, dtype=torch.int32, device="cuda"),
-               "payload_cap": exp["payload"].size, "sync_cap": exp["sync_len"].size}
-        assert enc["payload"].data_ptr() % 16 == 0
-        if mode == "shared":
-            enc["table"] = codec.table_lengths(_dev(torch, text_table(n_ary)), n_ary)
-        _uploaded[key] = enc
+        _uploaded[key] = _upload(torch, codec, mode, SEGMENTS, exp, n_ary, S)
     return _uploaded[key]
 
 
@@ -87,9 +92,9 @@ def _run(torch, codec, enc, rows, offs=None, cap=None, first=None):
     return out.cpu().numpy(), st.cpu().numpy(), offs
 
 
-def _check(codec, h, st, rows, offs, tag, bad=None):
-    """Every range not in `bad` (index -> expected status) is the slice of its segment; every other
-    byte is untouched; batch_status() is the lowest failing range's status."""
+def _check(codec, h, st, rows, offs, tag, bad=None, segs=SEGMENTS):
+    """Every range not in `bad` (index -> expected status) is the slice of its segment of `segs`;
+    every other byte is untouched; batch_status() is the lowest failing range's status."""
     bad = bad or {}
     asked = np.zeros(h.size, bool)
     for r, ((i, f, c), o) in enumerate(zip(np.asarray(rows).reshape(-1, 3).tolist(), offs)):
@@ -97,7 +102,7 @@ def _check(codec, h, st, rows, offs, tag, bad=None):
             assert st[r] == bad[r], tag + (r, (i, f, c), "status", int(st[r]))
             continue
         assert st[r] == 0, tag + (r, (i, f, c), int(st[r]))
-        assert np.array_equal(h[o: o + c], SEGMENTS[i][f: f + c]), tag + (r, (i, f, c), "decoded bytes")
+        assert np.array_equal(h[o: o + c], segs[i][f: f + c]), tag + (r, (i, f, c), "decoded bytes")
         asked[o: o + c] = True
     assert (h[~asked] == FILL).all(), tag + ("bytes outside the good ranges written",)
     assert codec.batch_status() == (bad[min(bad)] if bad else 0), tag + ("batch_status",)
