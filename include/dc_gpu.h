@@ -67,7 +67,12 @@ typedef struct dc_dtable {
     /* decoder tables indexed by the LSB-first window (the stream's bits in order):
      * dlut: next 12 bits -> bits | sym << 8; bits 0: a longer code (or no code), whose
      *       12-bit prefix has escape id sym; dlut2: [id << dlut2_k | next dlut2_k bits] ->
-     *       bits | sym << 8, 0: longer than 12 + dlut2_k bits or invalid (dlut2_k 0: none) */
+     *       bits | sym << 8, 0: longer than 12 + dlut2_k bits or invalid (dlut2_k 0: none).
+     * The second level exists when, with E = the escape ids (12-bit windows of no code of <= 12
+     * bits, an incomplete code's windows of no code at all among them) and K = max_bits - 12
+     * clamped to 1..8: 1 <= E <= 256, E << K <= DC_LUT2_CAP and max_bits <= 32. Then dlut2_k = K;
+     * otherwise dlut2_k = 0, dlut2 is all 0 and every code past 12 bits takes the canonical
+     * search. Past 256 escapes the id in dlut is the id mod 256 (unused: there is no dlut2). */
     uint16_t dlut[1 << DC_LUT_BITS];
     uint16_t dlut2[DC_LUT2_CAP];
     int32_t dlut2_k, dec_ready;   /* dec_ready: lut/dlut/dlut2/dlut14/dlut15 are current */
@@ -77,9 +82,15 @@ typedef struct dc_dtable {
      * bytes: n = 2 on all 256 values codes every byte as itself) */
     int32_t fixed8_affine, fixed8_lo, fixed8_count;
     /* dlut14: next 14 bits -> bits | sym << 8 for codes of <= 14 bits; bits 0: longer, sym =
-     * the escape id of its 12-bit prefix (as dlut); 16-B aligned for vector copies */
+     * the escape id of its 12-bit prefix (as dlut); 16-B aligned for vector copies. Codes of 13
+     * and 14 bits come from the second level, so they are resolved only when it exists and
+     * dlut2_k >= 2; otherwise their entries are escapes like those of longer codes */
     uint16_t dlut14[1 << DC_LUT14_BITS];
-    /* dlut15: the same on the next 15 bits (the fast decoder's table) */
+    /* dlut15: next 15 bits -> bits | sym << 8 for codes of <= 15 bits (the fast decoder's
+     * table); codes of 13..15 bits only when the second level exists and dlut2_k >= 3. Unlike
+     * dlut14, an entry of no resolved code is 0, not the escape id: the fast decoder tests the
+     * minimum over a chunk's entries against 0. So under a table whose longest code is 13 or 14
+     * bits (dlut2_k 1 or 2) every chunk that holds a code past 12 bits takes the exact redo */
     uint16_t dlut15[1 << DC_LUT15_BITS];
 } dc_dtable;
 
