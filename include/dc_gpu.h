@@ -219,9 +219,15 @@ uint64_t dc_huff_words_needed(uint64_t bit_base, uint64_t total_bits);
  * dc_huff_hist */
 int dc_huff_plan_offsets(dc_ctx *ctx, uint64_t *h_off, uint64_t max_entries, uint64_t *h_n);
 int dc_huff_block_hist(dc_ctx *ctx, uint16_t *h_bh, uint64_t max_entries);
-/* (4') the same without any host round trip (graph/timing friendly): a byte without a
- *     code or words_cap too small makes the kernels write nothing; read the outcome with
- *     dc_huff_pack_status() (synchronising). */
+/* (4') the same without any host round trip (graph/timing friendly): with a byte without a
+ *     code, or words_cap below the words the stream touches, the pack writes no code bit and no
+ *     sync entry. The plan kernels run before it looks, so d_words is not left as it was: the
+ *     words that hold a block's first bit, and the stream's partial last word, are zeroed where
+ *     they lie below words_cap; nothing else is written. Here words_cap need only cover the
+ *     stream's words (dc_huff_words_needed's slack is the decoder's; dc_huff_pack insists on it).
+ *     Read the outcome with dc_huff_pack_status() (synchronising). The outcome is the plan's: after
+ *     DC_E_CAPACITY every later pack of the same plan reads DC_E_CAPACITY too, so plan again before
+ *     packing into a larger buffer. */
 int dc_huff_pack_async(dc_ctx *ctx, const uint8_t *d_in, uint64_t n, const dc_dtable *d_table,
                        uint64_t bit_base, uint32_t *d_words, uint64_t words_cap,
                        uint64_t *d_sync_base, uint16_t *d_sync_len, uint32_t sync_syms);
