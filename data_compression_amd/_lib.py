@@ -99,6 +99,11 @@ def _declare_core(L):
         "dc_huff_plan": ([vp, P, P], i32),
         "dc_huff_encode_plan": ([vp, P, u64, i32, i32, P, P, P], i32),
         "dc_huff_table_plan": ([vp, P, i32, i32, P, P], i32),
+        "dc_huff_table_limit": ([vp, P, i32, i32, i32, P], i32),
+        "dc_huff_table_freq_limit": ([vp, P, i32, i32, i32, P], i32),
+        "dc_huff_table_plan_limit": ([vp, P, i32, i32, i32, P, P], i32),
+        "dc_huff_encode_plan_limit": ([vp, P, u64, i32, i32, i32, P, P, P], i32),
+        "dc_huff_limit_classes": ([i32, i32, C.POINTER(u32), u64], i32),
         "dc_small_huff_plan": ([vp, P, u64, i32, i32, P, P, P], i32),
         "dc_small_huff_pack_async": ([vp, P, u64, P, u64, P, u64, P, P, u32], i32),
         "dc_small_huff_symbols": ([vp, C.POINTER(u64)], i32),

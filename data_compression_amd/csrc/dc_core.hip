@@ -21,6 +21,7 @@
 #include "dc_nyb_batch_bound.h"
 #include "dc_small_batch_bound.h"
 #include "dc_batch_range.h"
+#include "dc_huff_limit.h"
 
 #define DC_VERSION "dc-mi355x 0.1 (gfx950)"
 #define DC_SYNC_GROUP 64
@@ -167,11 +168,12 @@ static __device__ __forceinline__ uint32_t fe_start_before(uint32_t pb, uint32_t
 // index so it is conflict free as well.
 // ------------------------------------------------------------------------------------
 struct TblLds;
+template <bool LIMIT = false>
 static __device__ void huff_table_body(TblLds &S, const uint64_t *__restrict__ freq, int freq_is_hist256,
                                        const int32_t *__restrict__ lens_in, int M, int nary,
                                        dc_dtable *__restrict__ T, dc_tree *__restrict__ tree,
                                        const uint64_t *plan_hist, uint64_t *__restrict__ d_total,
-                                       int *__restrict__ perr, int *__restrict__ perr_next);
+                                       int *__restrict__ perr, int *__restrict__ perr_next, int max_digits = 0);
 
 // The table build of a fused launch (HistFuse.T set): the last workgroup out, which holds the
 // final histogram, builds the code table and the encode plan total right away (no table
@@ -575,11 +577,15 @@ static __device__ void huff_merge_wave(const uint64_t *__restrict__ key, uint64_
 // also writes the encode plan of plan_hist (the histogram of the bytes to be packed): the
 // payload bits sum_s plan_hist[s] * nbits[s] (the reference's formula, n_ary_huffman.c:2485)
 // and the plan error flag (a byte present without a code), and clears the next plan's slot.
+// LIMIT (k_huff_table_limit alone; every other caller compiles the body without it): no code
+// longer than max_digits digits, by the rule of dc_huff_limit.h between the tree's depths and
+// the canonical stage.
+template <bool LIMIT>
 static __device__ void huff_table_body(TblLds &S, const uint64_t *__restrict__ freq, int freq_is_hist256,
                                        const int32_t *__restrict__ lens_in, int M, int nary,
                                        dc_dtable *__restrict__ T, dc_tree *__restrict__ tree,
                                        const uint64_t *plan_hist, uint64_t *__restrict__ d_total,
-                                       int *__restrict__ perr, int *__restrict__ perr_next)
+                                       int *__restrict__ perr, int *__restrict__ perr_next, int max_digits)
 {
     uint64_t *const s_key = S.key;
     uint64_t *const s_q2 = S.q2;
@@ -723,6 +729,41 @@ static __device__ void huff_table_body(TblLds &S, const uint64_t *__restrict__ f
             int d = 0, c = i;
             while (s_parent[c] != 0 && d < TBL_NODES) { ++d; c = s_parent[c]; }
             s_len[i] = d;
+        }
+        if (LIMIT) {
+            // Length limit (dc_huff_limit.h): when a depth passes D = max_digits, count the
+            // present symbols per length min(l, D), let one lane repair the counts, and hand the
+            // lengths out by rank: the sorted keys (count << 11 | index, ascending) read from the
+            // top are count descending, the higher symbol first among equals. The dummies (count
+            // 1, index >= leaves) sit right above the real symbols of count 1 and take no rank.
+            const int D = max_digits;
+            uint32_t *const lcnt = S.startv;   // [0 .. D]: free until the canonical stage
+            for (int d = t; d <= D; d += 256) lcnt[d] = 0;
+            __syncthreads();   // the depths, and lcnt zeroed
+            int over = 0;
+            for (int i = t; i < leaves; i += 256) {
+                const int L = s_len[i];
+                over |= L > D;
+                if (L > 0) atomicAdd(&lcnt[min(L, D)], 1u);
+            }
+            if (__syncthreads_or(over)) {   // (the barrier also completes lcnt)
+                if (t == 0) {
+                    if (dc_huff_limit_repair(nary, D, lcnt, (uint64_t)k, nullptr) != 0) s_bad = 1;
+                    uint32_t run = 0;   // lcnt[d] = symbols of length <= d (ranks below it)
+                    for (int d = 1; d <= D; ++d) { run += lcnt[d]; lcnt[d] = run; }
+                }
+                __syncthreads();
+                for (int p = t; p < items; p += 256) {
+                    const uint64_t key = s_key[p];
+                    const int idx = (int)(key & 2047u);
+                    if (idx >= leaves) continue;
+                    const uint32_t r = (uint32_t)(items - 1 - p) - ((key >> 11) == 1ull ? (uint32_t)dummies : 0u);
+                    int L = 1;
+                    while (L < D && r >= lcnt[L]) ++L;
+                    s_len[idx] = L;
+                }
+                __syncthreads();   // the keys' LDS becomes the length bitmaps; s_len is read by other threads
+            }
         }
     } else {
         for (int i = t; i < leaves; i += 256) s_len[i] = lens_in[i];
@@ -921,6 +962,19 @@ __global__ __launch_bounds__(256) void k_huff_table(const uint64_t *__restrict__
 {
     __shared__ TblLds S;
     huff_table_body(S, freq, freq_is_hist256, lens_in, M, nary, T, tree, plan_hist, d_total, perr, perr_next);
+}
+
+// k_huff_table with no code longer than max_digits digits (dc_huff_table_limit and its kin); the
+// table of a frequency array or byte histogram only (no given lengths, no node list)
+__global__ __launch_bounds__(256) void k_huff_table_limit(const uint64_t *__restrict__ freq, int freq_is_hist256, int M,
+                                                          int nary, int max_digits, dc_dtable *__restrict__ T,
+                                                          const uint64_t *__restrict__ plan_hist,
+                                                          uint64_t *__restrict__ d_total, int *__restrict__ perr,
+                                                          int *__restrict__ perr_next)
+{
+    __shared__ TblLds S;
+    huff_table_body<true>(S, freq, freq_is_hist256, nullptr, M, nary, T, nullptr, plan_hist, d_total, perr, perr_next,
+                          max_digits);
 }
 
 // dc_huff_plan: the encode plan of this context's last histogram under a table built elsewhere
@@ -6856,6 +6910,69 @@ int dc_huff_encode_plan(dc_ctx *c, const uint8_t *d_in, uint64_t n, int M, int n
     c->plan_total = d_total_bits;
     c->plan_ok = true;
     return DC_OK;
+}
+
+// ---- length-limited tables (dc_gpu.h "Length-limited tables"): the twins of the four calls
+// above with a cap in digits. max_digits 0 is the twin itself, kernels and all; a cap launches
+// k_huff_table_limit where the twin launches k_huff_table.
+int dc_huff_limit_classes(int nary, int max_digits, uint32_t *cnt, uint64_t k)
+{
+    if (!cnt || !dc_huff_limit_cap_ok(nary, max_digits, DC_MAX_DIGITS)) return DC_E_ARG;
+    return dc_huff_limit_repair(nary, max_digits, cnt, k, nullptr) == 0 ? DC_OK : DC_E_ARG;
+}
+
+static int table_limit_common(dc_ctx *c, const uint64_t *d_freq, int is_hist, int M, int nary, int max_digits,
+                              dc_dtable *d_table)
+{
+    if (!c || !d_freq || !d_table || M < 0 || M >= DC_MAX_SYMS || nary < 2 || nary > 256) return DC_E_ARG;
+    if (!dc_huff_limit_cap_ok(nary, max_digits, DC_MAX_DIGITS)) return DC_E_ARG;
+    table_written(c);
+    LAUNCH(c, "huff_table_limit", k_huff_table_limit, 1, 256, d_freq, is_hist, M, nary, max_digits, d_table,
+           (const uint64_t *)nullptr, (uint64_t *)nullptr, (int *)nullptr, (int *)nullptr);
+    return DC_OK;
+}
+
+int dc_huff_table_limit(dc_ctx *c, const uint64_t *d_hist, int M, int nary, int max_digits, dc_dtable *d_table)
+{
+    if (max_digits == 0) return dc_huff_table(c, d_hist, M, nary, d_table);
+    return table_limit_common(c, d_hist, 1, M, nary, max_digits, d_table);
+}
+
+int dc_huff_table_freq_limit(dc_ctx *c, const uint64_t *d_freq, int M, int nary, int max_digits, dc_dtable *d_table)
+{
+    if (max_digits == 0) return dc_huff_table_freq(c, d_freq, M, nary, d_table);
+    return table_limit_common(c, d_freq, 0, M, nary, max_digits, d_table);
+}
+
+int dc_huff_table_plan_limit(dc_ctx *c, const uint64_t *d_hist, int M, int nary, int max_digits, dc_dtable *d_table,
+                             uint64_t *d_total_bits)
+{
+    if (max_digits == 0) return dc_huff_table_plan(c, d_hist, M, nary, d_table, d_total_bits);
+    if (!c || !d_hist || !d_table || !d_total_bits || M < 0 || M >= DC_MAX_SYMS || nary < 2 || nary > 256) return DC_E_ARG;
+    if (!dc_huff_limit_cap_ok(nary, max_digits, DC_MAX_DIGITS)) return DC_E_ARG;
+    if (!c->hist_in && c->hist_n) return DC_E_STATE;
+    ++c->gen_p;
+    table_written(c);
+    LAUNCH(c, "huff_table_limit", k_huff_table_limit, 1, 256, d_hist, 1, M, nary, max_digits, d_table,
+           (const uint64_t *)c->d_hloc, d_total_bits, plan_err(c), plan_err_next(c));
+    c->plan_table = d_table;
+    c->plan_total = d_total_bits;
+    c->plan_ok = true;
+    return DC_OK;
+}
+
+int dc_huff_encode_plan_limit(dc_ctx *c, const uint8_t *d_in, uint64_t n, int M, int nary, int max_digits,
+                              uint64_t *d_hist, dc_dtable *d_table, uint64_t *d_total_bits)
+{
+    if (max_digits == 0) return dc_huff_encode_plan(c, d_in, n, M, nary, d_hist, d_table, d_total_bits);
+    if (!c || !d_table || !d_total_bits || M < 0 || M >= DC_MAX_SYMS || nary < 2 || nary > 256) return DC_E_ARG;
+    if (!dc_huff_limit_cap_ok(nary, max_digits, DC_MAX_DIGITS)) return DC_E_ARG;
+    // the histogram as dc_huff_hist launches it (its last workgroup builds no table), then the
+    // capped table and the plan of that histogram in one launch: the histogram kernels stay as
+    // they are, at the price of one launch more than the uncapped call
+    const int r = dc_huff_hist(c, d_in, n, d_hist);
+    if (r != DC_OK) return r;
+    return dc_huff_table_plan_limit(c, (const uint64_t *)c->d_hloc, M, nary, max_digits, d_table, d_total_bits);
 }
 
 // The per-block exclusive bit offsets of the last histogram's input under c->plan_table into

@@ -99,8 +99,28 @@ class Codec:
         check("dc_huff_hist", self.L.dc_huff_hist(self.ctx, _ptr(x), x.numel(), _ptr(out)))
         return out
 
-    def table(self, hist, n_ary: int, max_symbol_value: int = 258, out=None):
+    @staticmethod
+    def max_digits(n_ary: int, max_bits) -> int:
+        """The cap of the *_limit calls for a longest code of max_bits bits: max_bits // w digits
+        with w = ceil(log2 n_ary) bits a digit; 0 (no cap) for None. ValueError when not even
+        one digit fits."""
+        if max_bits is None:
+            return 0
+        w = max(int(n_ary) - 1, 1).bit_length()
+        d = int(max_bits) // w
+        if d < 1:
+            raise ValueError(f"max_bits {max_bits} holds no {w}-bit digit of an n_ary = {n_ary} code")
+        return d
+
+    def table(self, hist, n_ary: int, max_symbol_value: int = 258, out=None, max_bits=None):
+        """dc_huff_table; with max_bits, dc_huff_table_limit: no code longer than max_bits bits
+        (dc_gpu.h "Length-limited tables"; at n_ary 2, 15 keeps every code in the fast decoder's
+        table and 12 in the first-level table)."""
         out = out if out is not None else self._t(self.table_bytes)
+        if max_bits is not None:
+            check("dc_huff_table_limit", self.L.dc_huff_table_limit(
+                self.ctx, _ptr(hist), max_symbol_value, n_ary, self.max_digits(n_ary, max_bits), _ptr(out)))
+            return out
         check("dc_huff_table", self.L.dc_huff_table(self.ctx, _ptr(hist), max_symbol_value, n_ary, _ptr(out)))
         return out
 
@@ -108,8 +128,12 @@ class Codec:
         """An uninitialised device table (dc_dtable bytes), e.g. a broadcast target."""
         return self._t(self.table_bytes)
 
-    def table_freq(self, freq, n_ary: int, max_symbol_value: int, out=None):
+    def table_freq(self, freq, n_ary: int, max_symbol_value: int, out=None, max_bits=None):
         out = out if out is not None else self._t(self.table_bytes)
+        if max_bits is not None:
+            check("dc_huff_table_freq_limit", self.L.dc_huff_table_freq_limit(
+                self.ctx, _ptr(freq), max_symbol_value, n_ary, self.max_digits(n_ary, max_bits), _ptr(out)))
+            return out
         check("dc_huff_table_freq",
               self.L.dc_huff_table_freq(self.ctx, _ptr(freq), max_symbol_value, n_ary, _ptr(out)))
         return out
@@ -136,22 +160,37 @@ class Codec:
         """Whether the library has dc_huff_encode_plan (hist + table + plan in one launch)."""
         return hasattr(self.L, "dc_huff_encode_plan")
 
-    def encode_plan(self, x, n_ary: int, max_symbol_value: int = 258, hist=None, table=None, total=None):
+    def encode_plan(self, x, n_ary: int, max_symbol_value: int = 258, hist=None, table=None, total=None,
+                    max_bits=None):
         """hist -> table -> plan in one launch (dc_huff_encode_plan): the histogram kernel's
-        last workgroup builds the table and the payload bit count. Returns (hist, table, total)."""
+        last workgroup builds the table and the payload bit count. Returns (hist, table, total).
+        With max_bits: dc_huff_encode_plan_limit, two launches, no code longer than max_bits bits."""
         hist = hist if hist is not None else self._t(256, torch.int64)
         table = table if table is not None else self._t(self.table_bytes)
         total = total if total is not None else self._t(1, torch.int64)
+        if max_bits is not None:
+            check("dc_huff_encode_plan_limit", self.L.dc_huff_encode_plan_limit(
+                self.ctx, _ptr(x), x.numel(), max_symbol_value, n_ary, self.max_digits(n_ary, max_bits),
+                _ptr(hist), _ptr(table), _ptr(total)))
+            self._last_total = total
+            return hist, table, total
         check("dc_huff_encode_plan", self.L.dc_huff_encode_plan(self.ctx, _ptr(x), x.numel(), max_symbol_value, n_ary,
                                                                 _ptr(hist), _ptr(table), _ptr(total)))
         self._last_total = total
         return hist, table, total
 
-    def table_plan(self, hist, n_ary: int, max_symbol_value: int = 258, out=None, total=None):
+    def table_plan(self, hist, n_ary: int, max_symbol_value: int = 258, out=None, total=None, max_bits=None):
         """table of `hist` + the plan of this context's last hist() under it, one launch
-        (dc_huff_table_plan: a shard's encode after the all-reduce). Returns (table, total)."""
+        (dc_huff_table_plan: a shard's encode after the all-reduce). Returns (table, total).
+        With max_bits: dc_huff_table_plan_limit, no code longer than max_bits bits."""
         table = out if out is not None else self._t(self.table_bytes)
         total = total if total is not None else self._t(1, torch.int64)
+        if max_bits is not None:
+            check("dc_huff_table_plan_limit", self.L.dc_huff_table_plan_limit(
+                self.ctx, _ptr(hist), max_symbol_value, n_ary, self.max_digits(n_ary, max_bits), _ptr(table),
+                _ptr(total)))
+            self._last_total = total
+            return table, total
         check("dc_huff_table_plan", self.L.dc_huff_table_plan(self.ctx, _ptr(hist), max_symbol_value, n_ary,
                                                               _ptr(table), _ptr(total)))
         self._last_total = total
@@ -545,10 +584,13 @@ class Codec:
     def choose_sync(self, n: int, total_bits: int) -> int:
         return int(self.L.dc_huff_choose_sync(n, total_bits))
 
-    def encode(self, x, n_ary: int = 2, sync_syms: int | None = None, bit_base: int = 0):
-        """hist -> table -> plan -> pack on one device. Returns dict of device tensors."""
+    def encode(self, x, n_ary: int = 2, sync_syms: int | None = None, bit_base: int = 0, max_bits=None):
+        """hist -> table -> plan -> pack on one device. Returns dict of device tensors.
+        max_bits: no code longer than that many bits (encode_plan)."""
         n = x.numel()
-        if hasattr(self.L, "dc_huff_encode_plan"):
+        if max_bits is not None:
+            hist, tab, total = self.encode_plan(x, n_ary, max_bits=max_bits)
+        elif hasattr(self.L, "dc_huff_encode_plan"):
             hist, tab, total = self.encode_plan(x, n_ary)
         else:   # an older diagnostic library (tools/, DC_CORE_LIB): the three launches
             hist = self.hist(x)
@@ -777,15 +819,21 @@ class Codec:
                                       _ptr(out_off), nr, _ptr(buf), out.numel(), _ptr(status)))
         return out, out_off, status
 
-    def batch_table(self, x, n_ary: int = 2):
+    def batch_table(self, x, n_ary: int = 2, max_bits=None, cover: bool = False):
         """The table of the whole input x (device uint8): hist plus table, for
         encode_batch(..., table=...). dc_huff_hist wants a 16-B aligned input: a misaligned x is
-        cloned."""
+        cloned. max_bits: no code longer than that many bits (table()). cover: every one of the
+        256 byte values gets a code, whether x holds it or not: the histogram's entries are
+        raised to at least 1 on the device before the table (a sample then codes any later
+        segment; it deepens the tree, so give max_bits with it)."""
         if x.dtype != torch.uint8 or not x.is_contiguous():
             raise ValueError("batch_table input: contiguous uint8")
         if x.data_ptr() & 15:
             x = x.clone()
-        return self.table(self.hist(x), n_ary)
+        hist = self.hist(x)
+        if cover:
+            hist.clamp_(min=1)
+        return self.table(hist, n_ary, max_bits=max_bits)
 
     def table_get_lengths(self, tab):
         """dc_huff_table_get_lengths: the table's lengths in digits, entries 0 ..

@@ -202,6 +202,52 @@ int dc_huff_table_plan(dc_ctx *ctx, const uint64_t *d_hist, int max_symbol_value
  *     the histograms between the two, so it calls them separately). */
 int dc_huff_encode_plan(dc_ctx *ctx, const uint8_t *d_in, uint64_t n, int max_symbol_value, int n_ary,
                         uint64_t *d_hist, dc_dtable *d_table, uint64_t *d_total_bits);
+/* ---- Length-limited tables -------------------------------------------------------------
+ * The twins of (2a), (2b), (2+3 fused) and (1+2+3 fused) with max_digits added: a table none of
+ * whose codes is longer than max_digits base-n digits (max_digits * w bits, w = ceil(log2 n)).
+ * Each is asynchronous and makes no host read.
+ *   max_digits == 0   no cap: the call IS its twin, the same kernels and the same table.
+ *   max_digits > DC_MAX_DIGITS, or max_digits * w > 32: DC_E_ARG from the host, nothing launched.
+ *   fewer than k = #{count > 0} codes of max_digits digits exist (n^max_digits < k): the table's
+ *   status is DC_E_ARG (dc_huff_table_status), and nothing else about that table is promised.
+ * The rule, on the lengths l[] the uncapped call gives (DESIGN.md "Length-limited tables"): when
+ * no l passes D = max_digits the table is the uncapped one, byte for byte. Otherwise the present
+ * symbols are counted per length min(l, D), the counts are repaired (dc_huff_limit_classes below),
+ * and the symbols in the order (count descending, higher symbol value first among equal counts)
+ * take the lengths in ascending order: cnt[1] symbols length 1, the next cnt[2] length 2, ...
+ * Symbols of count 0 keep length 0. The canonical stage then runs on these lengths exactly as
+ * dc_huff_table_lengths would: lengths[] holds the capped lengths, and enc_*, code / nbits,
+ * first / count / start / syms, lim, min_len / max_len / max_bits, fixed8* and last_written
+ * follow from them; dec_ready is cleared; status is DC_OK. The plan of a capped table is the plan
+ * under the capped nbits. Every consumer (pack, all decoders, the shared-table batch calls, DCH1)
+ * takes such a table as it takes any other.
+ * Useful caps at n = 2: 15 bits, every code resolves from dlut15 (the S = 64 fast decoder redoes
+ * no chunk for its code lengths); 12 bits, every code resolves from the first-level dlut and no
+ * dlut2 exists. Caps of 13 or 14 bits are worse than 15 for the fast decoder: dlut2_k is then 1
+ * or 2, and every chunk with a code past 12 bits takes the exact redo (dlut15 above).
+ * Launches: dc_huff_table_limit, dc_huff_table_freq_limit and dc_huff_table_plan_limit ONE
+ * (k_huff_table_limit: one 256-thread workgroup, as their twins); dc_huff_encode_plan_limit TWO
+ * (the histogram as dc_huff_hist launches it, then k_huff_table_limit on it with the plan): one
+ * more than dc_huff_encode_plan, so that the histogram kernels are the uncapped ones. */
+int dc_huff_table_limit(dc_ctx *ctx, const uint64_t *d_hist, int max_symbol_value, int n_ary, int max_digits,
+                        dc_dtable *d_table);
+/* any max_symbol_value up to DC_MAX_SYMS - 1 */
+int dc_huff_table_freq_limit(dc_ctx *ctx, const uint64_t *d_freq, int max_symbol_value, int n_ary, int max_digits,
+                             dc_dtable *d_table);
+int dc_huff_table_plan_limit(dc_ctx *ctx, const uint64_t *d_hist, int max_symbol_value, int n_ary, int max_digits,
+                             dc_dtable *d_table, uint64_t *d_total_bits);
+int dc_huff_encode_plan_limit(dc_ctx *ctx, const uint8_t *d_in, uint64_t n, int max_symbol_value, int n_ary,
+                              int max_digits, uint64_t *d_hist, dc_dtable *d_table, uint64_t *d_total_bits);
+/* The repair of the length counts, pure host arithmetic (no device, no context; the table kernel
+ * runs the same function, csrc/dc_huff_limit.h). cnt[d], 1 <= d <= max_digits, holds the number
+ * of present symbols of length min(l, max_digits) and k their total (cnt[0] is not read), with
+ * B = n^max_digits and K = sum cnt[d] n^(max_digits - d):
+ *   demote   while K > B: one symbol of the largest d < max_digits with cnt[d] > 0 moves to d + 1;
+ *   promote  for d = max_digits down to 2: while cnt[d] > 0 and K + (n-1) n^(max_digits-d) <= B,
+ *            one symbol of length d moves to d - 1.
+ * Returns DC_OK with cnt repaired in place, or DC_E_ARG (cnt unchanged) for a NULL cnt, an invalid
+ * n_ary or max_digits (as the calls above; 0 is invalid here), sum cnt != k, or B < k. */
+int dc_huff_limit_classes(int n_ary, int max_digits, uint32_t *cnt, uint64_t k);
 /* (4) pack at global bit offset bit_base into d_words (word 0 = stream word bit_base/32,
  *     MSB-first bytes; 16-B aligned). Capacity: dc_huff_words_needed().
  *     Sync index (DESIGN.md "Sync index v1"), both arrays NULL for none: chunks of
