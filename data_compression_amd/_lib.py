@@ -130,6 +130,9 @@ def _declare_core(L):
         "dc_huff_batch_payload_bound": ([u64, u64], u64),
         "dc_huff_batch_sync_bound": ([u64, u64, u32], u64),
         "dc_huff_encode_batch": ([vp, P, P, u64, C.POINTER(HBatch)], i32),
+        "dc_huff_encode_batch_limit": ([vp, P, P, u64, i32, C.POINTER(HBatch)], i32),
+        "dc_huff_batch_lens_pack": ([vp, P, u64, P, P], i32),
+        "dc_huff_batch_lens_unpack": ([vp, P, u64, P], i32),
         "dc_huff_decode_batch": ([vp, C.POINTER(HBatch), P, P, u64], i32),
         "dc_huff_decode_batch_scatter": ([vp, C.POINTER(HBatch), P, P, P, u64], i32),
         "dc_huff_batch_status": ([vp], i32),

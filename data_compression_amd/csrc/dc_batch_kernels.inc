@@ -49,12 +49,22 @@ struct HbPlanLds {
     uint32_t h[256];
     uint32_t red[4];
 };
+// three workgroups a CU (hbatch_grid(c, count, 768)): the capped plan's class counts live in
+// tbl.startv (huff_table_body's limit stage), so the cap adds nothing here; the 256 B beside the
+// struct are what the limit stage's __syncthreads_or takes in the capped kernel
+static_assert(sizeof(HbPlanLds) == sizeof(TblLds) + 256 * 12 + 16 && 3 * (sizeof(HbPlanLds) + 256) <= 160 * 1024,
+              "k_hb_plan: three workgroups in a CU's 160 KiB of LDS");
 
+// LIMIT (dc_huff_encode_batch_limit): the segment's table is the one capped at max_digits digits
+// (huff_table_body<true>); a segment whose distinct bytes outnumber the codes of that length is
+// stored under a record of 256 zeros. The unlimited call compiles the body without the stage.
+template <bool LIMIT>
 __global__ __launch_bounds__(HB_THREADS) void k_hb_plan(const uint8_t *__restrict__ in, const uint64_t *__restrict__ in_off,
                                                         uint64_t count, int nary, uint32_t S, uint8_t *__restrict__ lens,
                                                         uint8_t *__restrict__ mode, uint32_t *__restrict__ bits,
                                                         uint64_t *__restrict__ psize, uint64_t *__restrict__ nchunks,
-                                                        int32_t *__restrict__ status, unsigned long long *__restrict__ first)
+                                                        int32_t *__restrict__ status, unsigned long long *__restrict__ first,
+                                                        int max_digits)
 {
     __shared__ HbPlanLds L;
     const int t = threadIdx.x;
@@ -97,12 +107,20 @@ __global__ __launch_bounds__(HB_THREADS) void k_hb_plan(const uint8_t *__restric
         L.h64[t] = L.h[t];
         __syncthreads();
         // lengths and canonical codes of symbols 0..258 exactly as k_huff_table (dc_huff_table)
-        huff_table_body(L.tbl, L.h64, 1, nullptr, 258, nary, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+        if constexpr (LIMIT) {
+            // inlined as the unlimited body is here (the compiler leaves a body with two callers out of
+            // line): the constant arguments drop the dc_dtable, tree and plan halves of it
+            [[clang::always_inline]] huff_table_body<true>(L.tbl, L.h64, 1, nullptr, 258, nary, nullptr, nullptr, nullptr,
+                                                           nullptr, nullptr, nullptr, max_digits);
+        } else {
+            huff_table_body(L.tbl, L.h64, 1, nullptr, 258, nary, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+        }
         uint32_t v = L.h[t] * L.tbl.nb[t];   // <= 65536 * 32
 #pragma unroll
         for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
         if ((t & 63) == 0) L.red[t >> 6] = v;
-        lens[i * 256 + t] = (uint8_t)L.tbl.len[t];
+        // (LIMIT: bad is a failed repair, n^D < k; what the body then left in len is no code)
+        lens[i * 256 + t] = (LIMIT && L.tbl.bad) ? (uint8_t)0 : (uint8_t)L.tbl.len[t];
         __syncthreads();
         if (t == 0) {
             const uint32_t cb = L.red[0] + L.red[1] + L.red[2] + L.red[3];

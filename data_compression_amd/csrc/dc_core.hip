@@ -738,15 +738,18 @@ static __device__ void huff_table_body(TblLds &S, const uint64_t *__restrict__ f
             // 1, index >= leaves) sit right above the real symbols of count 1 and take no rank.
             const int D = max_digits;
             uint32_t *const lcnt = S.startv;   // [0 .. D]: free until the canonical stage
-            for (int d = t; d <= D; d += 256) lcnt[d] = 0;
-            __syncthreads();   // the depths, and lcnt zeroed
             int over = 0;
-            for (int i = t; i < leaves; i += 256) {
-                const int L = s_len[i];
-                over |= L > D;
-                if (L > 0) atomicAdd(&lcnt[min(L, D)], 1u);
-            }
-            if (__syncthreads_or(over)) {   // (the barrier also completes lcnt)
+            for (int i = t; i < leaves; i += 256) over |= s_len[i] > D;   // (a thread's own depths)
+            // a table the cap does not bind in (every segment of a batch, back to back) pays this one
+            // barrier; the counts are taken only when it does
+            if (__syncthreads_or(over)) {
+                for (int d = t; d <= D; d += 256) lcnt[d] = 0;
+                __syncthreads();
+                for (int i = t; i < leaves; i += 256) {
+                    const int L = s_len[i];
+                    if (L > 0) atomicAdd(&lcnt[min(L, D)], 1u);
+                }
+                __syncthreads();
                 if (t == 0) {
                     if (dc_huff_limit_repair(nary, D, lcnt, (uint64_t)k, nullptr) != 0) s_bad = 1;
                     uint32_t run = 0;   // lcnt[d] = symbols of length <= d (ranks below it)
@@ -973,8 +976,9 @@ __global__ __launch_bounds__(256) void k_huff_table_limit(const uint64_t *__rest
                                                           int *__restrict__ perr_next)
 {
     __shared__ TblLds S;
-    huff_table_body<true>(S, freq, freq_is_hist256, nullptr, M, nary, T, nullptr, plan_hist, d_total, perr, perr_next,
-                          max_digits);
+    // (inlined here as in the capped batch plan, k_hb_plan<true>: no out-of-line copy of the capped body)
+    [[clang::always_inline]] huff_table_body<true>(S, freq, freq_is_hist256, nullptr, M, nary, T, nullptr, plan_hist, d_total,
+                                                   perr, perr_next, max_digits);
 }
 
 // dc_huff_plan: the encode plan of this context's last histogram under a table built elsewhere
@@ -6388,6 +6392,7 @@ __global__ __launch_bounds__(256) void k_copy_probe(const uint4 *__restrict__ sr
 
 #include "dc_range_kernels.inc"
 #include "dc_batch_kernels.inc"
+#include "dc_batch_lens_kernels.inc"
 #include "dc_batch_shared_kernels.inc"
 #include "dc_batch_range_kernels.inc"
 #include "dc_nyb_batch_kernels.inc"
@@ -7527,18 +7532,69 @@ static HbDecArgs hbatch_dec_args(const dc_hbatch *b, uint8_t *d_out, const uint6
                      d_status, first};
 }
 
-int dc_huff_encode_batch(dc_ctx *c, const uint8_t *d_in, const uint64_t *d_in_off, uint64_t count, const dc_hbatch *b)
+// the own-table encode: max_digits 0 is dc_huff_encode_batch (the plan compiled without the limit
+// stage), anything else a cap the host has checked
+static int hbatch_encode_own(dc_ctx *c, const uint8_t *d_in, const uint64_t *d_in_off, uint64_t count, int max_digits,
+                             const dc_hbatch *b)
 {
     unsigned long long *first;
     if (const int r = hbatch_encode_begin(c, b, true, d_in_off, count, &first)) return r > 0 ? DC_OK : r;
     uint64_t *const psize = c->d_hb + 2, *const nch = c->d_hb + 2 + count;
     const uint64_t g3 = hbatch_grid(c, count, 768), g2 = hbatch_grid(c, count, 512);   // LDS-bound: 3 and 2 per CU
-    LAUNCH(c, "hb_plan", k_hb_plan, g3, HB_THREADS, d_in, d_in_off, count, (int)b->n_ary, b->sync_syms, b->d_lens, b->d_mode,
-           b->d_bits, psize, nch, b->d_status, first);
+    if (max_digits == 0)
+        LAUNCH(c, "hb_plan", k_hb_plan<false>, g3, HB_THREADS, d_in, d_in_off, count, (int)b->n_ary, b->sync_syms, b->d_lens,
+               b->d_mode, b->d_bits, psize, nch, b->d_status, first, 0);
+    else
+        LAUNCH(c, "hb_plan_limit", k_hb_plan<true>, g3, HB_THREADS, d_in, d_in_off, count, (int)b->n_ary, b->sync_syms, b->d_lens,
+               b->d_mode, b->d_bits, psize, nch, b->d_status, first, max_digits);
     if (const int r = hbatch_scans(c, b, psize, nch)) return r;
     LAUNCH(c, "hb_pack", k_hb_pack, g2, HB_THREADS, d_in, d_in_off, count, (int)b->n_ary, hbatch_w(b->n_ary), b->sync_syms,
            (const uint8_t *)b->d_lens, (const uint8_t *)b->d_mode, (const uint64_t *)b->d_pay_off, b->d_payload,
            b->payload_cap, (const uint64_t *)b->d_sync_off, b->d_sync_len, b->sync_cap, b->d_status, first);
+    return DC_OK;
+}
+
+int dc_huff_encode_batch(dc_ctx *c, const uint8_t *d_in, const uint64_t *d_in_off, uint64_t count, const dc_hbatch *b)
+{
+    return hbatch_encode_own(c, d_in, d_in_off, count, 0, b);
+}
+
+int dc_huff_encode_batch_limit(dc_ctx *c, const uint8_t *d_in, const uint64_t *d_in_off, uint64_t count, int max_digits,
+                               const dc_hbatch *b)
+{
+    if (max_digits == 0) return dc_huff_encode_batch(c, d_in, d_in_off, count, b);
+    if (!b || !dc_huff_limit_cap_ok(b->n_ary, max_digits, DC_MAX_DIGITS)) return DC_E_ARG;
+    return hbatch_encode_own(c, d_in, d_in_off, count, max_digits, b);
+}
+
+// the nybble form of the lens records (dc_batch_lens_kernels.inc): 16 lanes a record, 8 workgroups a CU
+static int hbatch_lens_args(dc_ctx *c, const uint8_t *d_lens, const uint8_t *d_lens4, uint64_t count)
+{
+    if (!c) return DC_E_ARG;
+    if (count == 0) return 1;
+    if (!d_lens || !d_lens4 || count > DC_RANGES_MAX) return DC_E_ARG;
+    if (((uintptr_t)d_lens & 15) || ((uintptr_t)d_lens4 & 7)) return DC_E_ARG;
+    const uintptr_t a = (uintptr_t)d_lens, a4 = (uintptr_t)d_lens4;
+    if (a < a4 + 128 * count && a4 < a + 256 * count) return DC_E_ARG;   // the two buffers overlap
+    return DC_OK;
+}
+
+int dc_huff_batch_lens_pack(dc_ctx *c, const uint8_t *d_lens, uint64_t count, uint8_t *d_lens4, int32_t *d_status)
+{
+    if (const int r = hbatch_lens_args(c, d_lens, d_lens4, count)) return r > 0 ? DC_OK : r;
+    if (!d_status) return DC_E_ARG;
+    unsigned long long *first;
+    if (const int r = hbatch_begin(c, 0, &first)) return r;
+    const uint64_t grid = hbatch_grid(c, (count + HBL_RECS - 1) / HBL_RECS, 2048);
+    LAUNCH(c, "hb_lens_pack", k_hb_lens_pack, grid, HB_THREADS, d_lens, count, d_lens4, d_status, first);
+    return DC_OK;
+}
+
+int dc_huff_batch_lens_unpack(dc_ctx *c, const uint8_t *d_lens4, uint64_t count, uint8_t *d_lens)
+{
+    if (const int r = hbatch_lens_args(c, d_lens, d_lens4, count)) return r > 0 ? DC_OK : r;
+    const uint64_t grid = hbatch_grid(c, (count + HBL_RECS - 1) / HBL_RECS, 2048);
+    LAUNCH(c, "hb_lens_unpack", k_hb_lens_unpack, grid, HB_THREADS, d_lens4, count, d_lens);
     return DC_OK;
 }
 

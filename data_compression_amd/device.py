@@ -722,7 +722,7 @@ class Codec:
         return v
 
     def encode_batch(self, x, offsets, n_ary: int = 2, sync_syms: int = 64, payload=None, sync_len=None,
-                     payload_cap=None, sync_cap=None, table=None):
+                     payload_cap=None, sync_cap=None, table=None, max_bits=None):
         """dc_huff_encode_batch: segment i = x[offsets[i]:offsets[i+1]] (device uint8 x, int64
         offsets of count + 1 entries, any alignment, each segment <= 65536 bytes) coded under a
         table of its own, or stored when that is not smaller. Asynchronous, no host read; the
@@ -733,9 +733,16 @@ class Codec:
         table: a device table (table(), table_lengths(), batch_table()) of the same n_ary that
         codes EVERY segment (dc_huff_encode_batch_shared): no table work per segment and no
         lens record; a segment holding a byte without a code under it is stored. The result
-        then carries "table": table and "lens": None."""
+        then carries "table": table and "lens": None.
+        max_bits (own tables only): no code of any segment's table longer than that many bits
+        (dc_huff_encode_batch_limit); a segment with more distinct bytes than such codes is
+        stored under a record of zeros. With table=, the cap belongs to batch_table(): a
+        ValueError. The result carries "max_bits"."""
         if x.dtype != torch.uint8 or not x.is_contiguous():
             raise ValueError("encode_batch input: contiguous uint8")
+        if table is not None and max_bits is not None:
+            raise ValueError("encode_batch: max_bits caps the per-segment tables; cap a shared table in batch_table()")
+        max_digits = self.max_digits(n_ary, max_bits)
         offsets = self._i64(offsets, range(1, 1 << 62), "encode_batch offsets")
         count = offsets.numel() - 1
         pb, sb = self.batch_bounds(x.numel(), count, sync_syms)
@@ -746,7 +753,7 @@ class Codec:
                "mode": self._t(max(count, 1))[:count],
                "bits": self._t(max(count, 1), torch.int32)[:count], "pay_off": self._t(count + 1, torch.int64),
                "payload": payload, "sync_off": self._t(count + 1, torch.int64), "sync_len": sync_len,
-               "status": self._t(max(count, 1), torch.int32)[:count]}
+               "status": self._t(max(count, 1), torch.int32)[:count], "max_bits": max_bits}
         b = self._hbatch(enc, payload_cap, sync_cap)
         enc["payload_cap"], enc["sync_cap"] = int(b.payload_cap), int(b.sync_cap)
         if table is not None:
@@ -754,13 +761,17 @@ class Codec:
             check("dc_huff_encode_batch_shared",
                   self.L.dc_huff_encode_batch_shared(self.ctx, _ptr(x), _ptr(offsets), count, _ptr(table), C.byref(b)))
             return enc
+        if max_bits is not None:
+            check("dc_huff_encode_batch_limit",
+                  self.L.dc_huff_encode_batch_limit(self.ctx, _ptr(x), _ptr(offsets), count, max_digits, C.byref(b)))
+            return enc
         check("dc_huff_encode_batch", self.L.dc_huff_encode_batch(self.ctx, _ptr(x), _ptr(offsets), count, C.byref(b)))
         return enc
 
     def encode_blocks(self, x, block: int = 65536, **kw):
         """encode_batch of x cut into independent blocks of `block` bytes (the last shorter),
         a table each: the reference's own block design (n_ary_huffman.c:1210-1255); with
-        table=..., all under that one table."""
+        table=..., all under that one table; with max_bits=..., each table capped."""
         if not 0 < block <= self.SEG_MAX:
             raise ValueError("encode_blocks: 0 < block <= 65536")
         return self.encode_batch(x, self._block_offsets(x, block), **kw)
@@ -819,6 +830,33 @@ class Codec:
                                       _ptr(out_off), nr, _ptr(buf), out.numel(), _ptr(status)))
         return out, out_off, status
 
+    def batch_lens_pack(self, enc):
+        """dc_huff_batch_lens_pack of enc["lens"] (an own-table batch): (lens4, status), a count x
+        128 uint8 device tensor (byte j of a record = lens[2j] << 4 | lens[2j + 1]) and an int32
+        one. A record holding a length above 15 is written as zeros with DC_E_CODE_TOO_LONG (-3)
+        in its status and the lowest such index in batch_status(); none does when the batch was
+        encoded under a cap of at most 15 digits. Asynchronous, one launch."""
+        lens = enc["lens"]
+        if lens is None:
+            raise ValueError("batch_lens_pack: a batch under a shared table has no lens records")
+        count = enc["count"]
+        lens4 = self._t(max(count, 1) * 128).view(max(count, 1), 128)[:count]
+        status = self._t(max(count, 1), torch.int32)[:count]
+        check("dc_huff_batch_lens_pack",
+              self.L.dc_huff_batch_lens_pack(self.ctx, _ptr(lens), count, _ptr(lens4), _ptr(status)))
+        return lens4, status
+
+    def batch_lens_unpack(self, lens4):
+        """dc_huff_batch_lens_unpack: the count x 256 uint8 lens records of a count x 128 nybble
+        tensor, to be put back as enc["lens"] before a decode. Asynchronous, one launch."""
+        if lens4.dtype != torch.uint8 or not lens4.is_cuda or not lens4.is_contiguous() or lens4.dim() != 2 \
+                or lens4.shape[1] != 128:
+            raise ValueError("batch_lens_unpack: a contiguous count x 128 uint8 device tensor")
+        count = lens4.shape[0]
+        lens = self._t(max(count, 1) * 256).view(max(count, 1), 256)[:count]
+        check("dc_huff_batch_lens_unpack", self.L.dc_huff_batch_lens_unpack(self.ctx, _ptr(lens4), count, _ptr(lens)))
+        return lens
+
     def batch_table(self, x, n_ary: int = 2, max_bits=None, cover: bool = False):
         """The table of the whole input x (device uint8): hist plus table, for
         encode_batch(..., table=...). dc_huff_hist wants a 16-B aligned input: a misaligned x is
@@ -846,7 +884,8 @@ class Codec:
 
     def batch_status(self) -> int:
         """0, or the status of the lowest-numbered failing segment of the last batch call on this
-        codec (encode_batch, decode_batch, decode_batch_ranges, nyb_compress_batch,
+        codec (encode_batch with or without max_bits, batch_lens_pack, decode_batch,
+        decode_batch_ranges, nyb_compress_batch,
         nyb_decompress_batch_into, small_compress_batch, small_decompress_batch_into),
         synchronising."""
         return int(self.L.dc_huff_batch_status(self.ctx))

@@ -456,6 +456,43 @@ uint64_t dc_huff_batch_sync_bound(uint64_t total_bytes, uint64_t count, uint32_t
  * without a launch. At most DC_RANGES_MAX segments. */
 int dc_huff_encode_batch(dc_ctx *ctx, const uint8_t *d_in, const uint64_t *d_in_off, uint64_t count,
                          const dc_hbatch *batch);
+/* Encode with length-limited tables: dc_huff_encode_batch exactly (the same arrays, bounds,
+ * statuses and launches, no host read), but segment i's table is the one dc_huff_table_limit(h, 258,
+ * n_ary, max_digits) builds from its histogram ("Length-limited tables" above):
+ *   lens   the first 256 lengths of that capped table; none passes max_digits.
+ *   mode, bits  decided under the capped code: Huffman when sum h[s] * nbits[s] < 8 len, else
+ *          stored. A segment the unlimited call codes may be stored here (4096 bytes holding all
+ *          256 values at n = 2, max_digits = 8: every length is 8, the bits are 8 len).
+ *   no code  fewer than k = #{h > 0} codes of max_digits digits exist (n^max_digits < k): the
+ *          segment is stored, its status is DC_OK (a stored segment always decodes) and its lens
+ *          record is 256 zeros; the decoders read lens for mode 1 alone.
+ * Payload, offsets, sync entries, pads and caps mean what they mean above, and every decode call
+ * takes such a batch as it takes any other: the code is rebuilt from lens.
+ *   max_digits == 0   the call IS dc_huff_encode_batch: the same kernels, every array byte-identical.
+ *   max_digits > DC_MAX_DIGITS, or max_digits * w > 32: DC_E_ARG from the host, nothing launched.
+ * With max_digits <= 15 every record has a nybble form (below). The cap is repaired by one lane
+ * per segment, a few dozen serial steps when it binds. */
+int dc_huff_encode_batch_limit(dc_ctx *ctx, const uint8_t *d_in, const uint64_t *d_in_off, uint64_t count,
+                               int max_digits, const dc_hbatch *batch);
+/* ---- Huffman batch v1: nybble records ---------------------------------------------------------
+ * The lens records in half the bytes, once no length passes 15 (the reference's "256 nybbles",
+ * n_ary_huffman.c:2415-2420). A storage form only: the batch calls read 256-byte records, so a
+ * caller packs after the encode and unpacks before the decode. Record i is 128 bytes at
+ * d_lens4 + 128 i; byte j = lens[2j] << 4 | lens[2j + 1] (the high nybble first, as the bitstream
+ * and the nybble codec put things).
+ * Pack: d_status[i] (i32, count entries) = DC_OK, or DC_E_CODE_TOO_LONG for a record that holds a
+ * length above 15: its 128 bytes are written as zeros, every other record is unaffected, and the
+ * lowest failing index goes to the context's first-failure slot (dc_huff_batch_status). A zero
+ * record unpacks to all-zero lengths, under which the decoders fail a mode-1 segment with
+ * DC_E_STREAM: never a wrong byte. Every record of dc_huff_encode_batch_limit with max_digits <= 15
+ * packs; an uncapped record packs when the segment's tree is at most 15 deep.
+ * Unpack: always succeeds, writes all 256 bytes of every record, and leaves the first-failure slot
+ * as it is.
+ * Both: asynchronous, one launch for any count, no host read; count 0 returns DC_OK without a
+ * launch; DC_E_ARG for more than DC_RANGES_MAX records, a NULL pointer with count > 0, d_lens not
+ * 16-B or d_lens4 not 8-B aligned, or buffers that overlap. DC_OPT_BATCH_GRID sizes their grids. */
+int dc_huff_batch_lens_pack(dc_ctx *ctx, const uint8_t *d_lens, uint64_t count, uint8_t *d_lens4, int32_t *d_status);
+int dc_huff_batch_lens_unpack(dc_ctx *ctx, const uint8_t *d_lens4, uint64_t count, uint8_t *d_lens);
 /* Decode: segment i -> d_out[d_out_off[i] .. d_out_off[i + 1]) (device u64, count + 1 entries,
  * any alignment). The length asked for must be the segment's (the format does not store it).
  * Asynchronous, one launch. No byte of d_out outside the requested ranges is written, and none

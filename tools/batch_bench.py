@@ -22,9 +22,18 @@ of bench.py (synth.device_text, seed 0xC2, n = 2, S = 64), one process:
           `--rounds` rounds of HIP-event windows of at least 20 ms; asserts that at 4096 ranges of
           the 64 KiB blocks the range call is faster. Then own tables at 65536 ranges, sorted by
           segment and not, and Codec.decode_ranges on the single stream of the same text.
+  limit   (only on request) own tables capped per segment (encode_blocks(..., max_bits=)): the
+          unlimited, 15-bit and 12-bit batches of both block sizes alternating inside every round.
+          Per table: the whole encode and the decode (HIP-event windows), the plan and pack
+          kernels' own times (dc_ctx_timings, one call a round), the payload bytes, how many
+          segments the cap binds in (their unlimited record is deeper) and how many come out
+          stored, the stored size with 256-byte and with 128-byte lens records, and the
+          batch_lens_pack / batch_lens_unpack times. Every figure is the median of `--rounds`
+          rounds with its (min, max): the spread a call shows against itself.
 Every result is checked against the input before it is timed. One JSON line per result.
     timeout 900 python tools/batch_bench.py [--size BYTES] [--steps K] [--rounds R] [--only blocks,loop,shared]
     timeout 900 python tools/batch_bench.py --only ranges
+    timeout 900 python tools/batch_bench.py --only limit
 """
 import argparse
 import ctypes
@@ -222,6 +231,75 @@ if "shared" in a.only:
             assert med["shared_decode"] < med["own_decode"], "the shared-table decode is not faster than the own-table decode"
             assert size["shared"] < size["own"], "the shared-table form is not smaller than the own-table form"
         del encs, bufs
+    del out
+
+if "limit" in a.only:
+    CAPS = (None, 15, 12)
+    cap_name = lambda cap: "unlimited" if cap is None else f"{cap}bit"
+    out = torch.empty(n, dtype=torch.uint8, device=dev)
+    for block in (65536, 4096):
+        count = (n + block - 1) // block
+        pb, sb = c.batch_bounds(n, count, S)
+        bufs = {cap: (torch.empty(pb, dtype=torch.uint8, device=dev), torch.empty(sb, dtype=torch.int16, device=dev))
+                for cap in CAPS}
+
+        def encode(cap):
+            return c.encode_blocks(x, block=block, n_ary=2, sync_syms=S, payload=bufs[cap][0], sync_len=bufs[cap][1],
+                                   max_bits=cap)
+
+        encs, packed = {}, {}
+        for cap in CAPS:
+            enc = encs[cap] = encode(cap)
+            assert c.batch_status() == 0
+            lens4, st = c.batch_lens_pack(enc)
+            packs = c.batch_status() == 0
+            back = c.batch_lens_unpack(lens4)
+            assert not packs or torch.equal(back, enc["lens"]), "the nybble records do not unpack to the lens records"
+            assert packs or cap is None, "a record capped at 15 bits or fewer did not pack"
+            out.zero_()
+            c.decode_batch(dict(enc, lens=back) if packs else enc, out=out, out_off=enc["offsets"])   # from the stored form
+            assert c.batch_status() == 0 and torch.equal(out, x), cap_name(cap) + ": batch round trip differs from the input"
+            packed[cap] = lens4
+            pay, idx = int(enc["pay_off"][-1]), int(enc["sync_off"][-1])
+            depth = encs[None]["lens"].max(dim=1).values
+            emit(what="limit_size", table=cap_name(cap), block=block, count=count, payload_bytes=pay,
+                 payload_vs_unlimited_pct=round(100 * (pay / int(encs[None]["pay_off"][-1]) - 1), 4),
+                 deepest_record=int(enc["lens"].max()), binding_segments=0 if cap is None else int((depth > cap).sum()),
+                 stored_segments=int((enc["mode"] == 0).sum()), records_pack=packs,
+                 unpackable_records=int((st != 0).sum()),
+                 stored_bytes_lens256=pay + 2 * idx + count * (5 + 256), stored_bytes_lens128=pay + 2 * idx + count * (5 + 128))
+        fns = {}
+        for cap in CAPS:
+            k = cap_name(cap)
+            fns["encode_" + k] = lambda cap=cap: encode(cap)
+            fns["decode_" + k] = lambda cap=cap: c.decode_batch(encs[cap], out=out, out_off=encs[cap]["offsets"])
+            fns["lens_pack_" + k] = lambda cap=cap: c.batch_lens_pack(encs[cap])
+            fns["lens_unpack_" + k] = lambda cap=cap: c.batch_lens_unpack(packed[cap])
+        for fn in fns.values():
+            fn()
+        torch.cuda.synchronize()
+        t = {k: [] for k in fns}
+        stages = {cap_name(cap): {} for cap in CAPS}
+        for _ in range(a.rounds):
+            for k, fn in fns.items():
+                t[k].append(ev_ms(fn, a.steps))
+            for cap in CAPS:   # the kernels' own times (events around each launch: slower end to end, so apart)
+                c.timing(True)
+                encode(cap)
+                for name, ms in c.timings():
+                    stages[cap_name(cap)].setdefault(name.replace("_limit", ""), []).append(ms)
+                c.timing(False)
+        med = {k: round(statistics.median(v), 4) for k, v in t.items()}
+        emit(what="limit_time", block=block, count=count, ms=med,
+             min_max_ms={k: (round(min(v), 4), round(max(v), 4)) for k, v in t.items()},
+             decode_15bit_over_unlimited=round(med["decode_15bit"] / med["decode_unlimited"], 4),
+             decode_12bit_over_unlimited=round(med["decode_12bit"] / med["decode_unlimited"], 4),
+             encode_15bit_over_unlimited=round(med["encode_15bit"] / med["encode_unlimited"], 4),
+             encode_12bit_over_unlimited=round(med["encode_12bit"] / med["encode_unlimited"], 4))
+        emit(what="limit_stages", block=block, count=count,
+             ms={k: {s: round(statistics.median(v), 4) for s, v in d.items()} for k, d in stages.items()},
+             min_max_ms={k: {s: (round(min(v), 4), round(max(v), 4)) for s, v in d.items()} for k, d in stages.items()})
+        del encs, bufs, packed
     del out
 
 if "ranges" in a.only:
