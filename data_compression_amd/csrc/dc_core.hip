@@ -2181,7 +2181,10 @@ __global__ __launch_bounds__(256) void k_fe_pack(const uint8_t *__restrict__ in,
         } else {
             for (uint32_t i = t + 1; i < last_plain; i += 256) { dst[i] = bswap32(s_stage[i]); s_stage[i] = 0u; }
         }
-        if (t == 0) {
+        // (nw_blk = 0: a shard's one-byte last block, a pair's start, on a word boundary. It has
+        // no word: its first word would be the one at index = the stream's words, which words_cap
+        // need not hold)
+        if (t == 0 && nw_blk > 0) {
             atomicOr(&dst[sh], bswap32(s_stage[sh]));
             s_stage[sh] = 0u;
         }

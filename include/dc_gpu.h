@@ -305,7 +305,11 @@ int dc_huff_pack_status_gen(dc_ctx *ctx, const dc_dtable *d_table, uint32_t gen)
  * output falls back to LITERAL (small_compression.c:655-662), when every byte value occurs in
  * M (the pack marks a pair's start with a byte value that has no code), or when a 32 KiB block
  * codes to more bits than the pack's stage holds beside its sync list; the caller then runs
- * the two stages. dc_small_huff_symbols reads the symbol count of M (synchronising). */
+ * the two stages. dc_small_huff_symbols reads the symbol count of M (synchronising).
+ * words_cap need only cover the words the stream has a bit in (as dc_huff_pack_async), and no
+ * word from words_cap on is touched. After DC_E_FALLBACK the outputs are not as they were: the
+ * plan kernels have zeroed the block-boundary words and length dwords, and for an over-long block
+ * the other blocks have been packed; nothing outside the documented sizes is written. */
 int dc_small_huff_plan(dc_ctx *ctx, const uint8_t *d_in, uint64_t n, int max_symbol_value, int n_ary,
                        uint64_t *d_hist, dc_dtable *d_table, uint64_t *d_total_bits);
 int dc_small_huff_pack_async(dc_ctx *ctx, const uint8_t *d_in, uint64_t n, const dc_dtable *d_table,
@@ -329,7 +333,13 @@ int dc_small_huff_symbols(dc_ctx *ctx, uint64_t *h_symbols);
  * which belongs to the whole stream (the caller's). Sizes: d_sync_len / d_sync_base as for
  * dc_small_huff_pack_async (n + 1 symbols, u16 lengths rounded up to whole dwords + 2 entries);
  * d_gsync_len / d_gsync_base for n + 1 + 2 S symbols (the shard's chunks counted from c0 & ~1,
- * plus the partial chunks it shares at either end), the lengths rounded the same way. */
+ * plus the partial chunks it shares at either end), the lengths rounded the same way.
+ * n >= 2; d_in 16-B aligned. words_cap: the words the shard has a bit in, counted from the word of
+ * d_shard[0]; no word from words_cap on is touched. (A last 32 KiB block that is one byte, a space
+ * before the letter after the shard, holds no symbol; when it starts on a word boundary it has no
+ * word, and the pack leaves the word at index = the shard's words alone.) Entry 0 of d_gsync_len
+ * is written as zero when c0 is odd, and so is the entry after the last chunk when that chunk is
+ * even: the plan zeroes whole dwords. */
 int dc_small_huff_shard_hist(dc_ctx *ctx, const uint8_t *d_in, uint64_t n, const int64_t *d_shard,
                              uint64_t *d_hist);
 int dc_small_huff_shard_pack_async(dc_ctx *ctx, const uint8_t *d_in, uint64_t n, const dc_dtable *d_table,
