@@ -886,11 +886,8 @@ __global__ __launch_bounds__(256) void k_huff_pack_dma(const uint8_t *__restrict
 #pragma unroll
         for (int k = 0; k < PACK_PIECES; ++k) {
             const uint32_t w4[4] = {blkv[k].x, blkv[k].y, blkv[k].z, blkv[k].w};
-            uint32_t s0 = 0, s1 = 0;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) s0 += L.nb8[(w4[i >> 2] >> (8 * (i & 3))) & 255u];
-#pragma unroll
-            for (int i = 8; i < 16; ++i) s1 += L.nb8[(w4[i >> 2] >> (8 * (i & 3))) & 255u];
+            uint32_t s0, s1;
+            pack_piece_bits(w4, L.nb8, s0, s1);
             Hk[k] = s0;
             Tk[k] = s0 + s1;
             __builtin_amdgcn_sched_barrier(0);
@@ -929,86 +926,11 @@ __global__ __launch_bounds__(256) void k_huff_pack_dma(const uint8_t *__restrict
             uint32_t w4[4] = {blkv[k].x, blkv[k].y, blkv[k].z, blkv[k].w};
             asm volatile("" : "+v"(w4[0]), "+v"(w4[1]), "+v"(w4[2]), "+v"(w4[3]));
             const uint32_t rel = (uint32_t)(As - org);
-            auto emit = [&](uint64_t acc, uint32_t nb, uint32_t pos) {
-                const uint64_t al = acc << ((64u - nb) & 63u);
-                const uint32_t hi = (uint32_t)(al >> 32), lo = (uint32_t)al, r = pos & 31u, wi = pos >> 5;
-                atomicOr(&L.stage[wi], hi >> r);
-                atomicOr(&L.stage[wi + 1], __builtin_amdgcn_alignbit(hi, lo, r));
-                atomicOr(&L.stage[wi + 2], __builtin_amdgcn_alignbit(lo, 0u, r));
-            };
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const uint32_t Th = h ? Tk[k] - Hk[k] : Hk[k];
-                const uint32_t pos = h ? rel + Hk[k] : rel;
-                if (!qmode && Th <= 64u) {
-                    uint64_t acc = 0;
-#pragma unroll
-                    for (int i = 8 * h; i < 8 * h + 8; ++i) {
-                        const uint2 e = L.tab[(w4[i >> 2] >> (8 * (i & 3))) & 255u];
-                        acc = (acc << e.y) | e.x;
-                    }
-                    emit(acc, Th, pos);
-                } else {
-                    uint32_t pq = pos;
-#pragma unroll
-                    for (int qq = 0; qq < 2; ++qq) {
-                        uint2 e[4];
-                        uint32_t nq = 0;
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) {
-                            const int bi = 8 * h + 4 * qq + i;
-                            const uint32_t wv = qq ? w4[2 * h + 1] : w4[2 * h];
-                            e[i] = L.tab[(wv >> (8 * (bi & 3))) & 255u];
-                            nq += e[i].y;
-                        }
-                        if (nq <= 64u) {
-                            uint64_t acc = 0;
-#pragma unroll
-                            for (int i = 0; i < 4; ++i) acc = (acc << e[i].y) | e[i].x;
-                            emit(acc, nq, pq);
-                            pq += nq;
-                        } else {
-#pragma unroll
-                            for (int i = 0; i < 4; ++i) { emit(e[i].x, e[i].y, pq); pq += e[i].y; }
-                        }
-                    }
-                }
-            }
+            pack_code_piece(L.stage, L.tab, w4, qmode, Hk[k], Tk[k], rel, [](int, uint32_t) {});
             __builtin_amdgcn_sched_barrier(0);
         }
         lds_barrier();
-        const uint32_t last_plain = ((run & 31) != 0) ? nwa - 1 : nwa;
-        uint32_t *dst = out + (blk_first_word - word_base) - sh;
-        if (vec_out) {
-            const uint32_t nq = last_plain >> 2;
-            for (uint32_t q = 1 + t; q < nq; q += 256) {
-                uint4 *const sq = reinterpret_cast<uint4 *>(&L.stage[4 * q]);
-                const uint4 v = *sq;
-                *sq = make_uint4(0u, 0u, 0u, 0u);
-                uint4 *const d4 = reinterpret_cast<uint4 *>(dst + 4 * q);
-                __builtin_nontemporal_store(bswap32(v.x), &d4->x);
-                __builtin_nontemporal_store(bswap32(v.y), &d4->y);
-                __builtin_nontemporal_store(bswap32(v.z), &d4->z);
-                __builtin_nontemporal_store(bswap32(v.w), &d4->w);
-            }
-            const uint32_t hend = last_plain < 4u ? last_plain : 4u;
-            if (t < 4 && (uint32_t)t > sh && (uint32_t)t < hend) { dst[t] = bswap32(L.stage[t]); L.stage[t] = 0u; }
-            const uint32_t tb = nq > 0 ? 4 * nq : 4u;
-            if (t >= 8 && t < 12 && tb + (t - 8) < last_plain) {
-                dst[tb + (t - 8)] = bswap32(L.stage[tb + (t - 8)]);
-                L.stage[tb + (t - 8)] = 0u;
-            }
-        } else {
-            for (uint32_t i = t + 1; i < last_plain; i += 256) { dst[i] = bswap32(L.stage[i]); L.stage[i] = 0u; }
-        }
-        if (t == 0) {
-            atomicOr(&dst[sh], bswap32(L.stage[sh]));
-            L.stage[sh] = 0u;
-        }
-        if (t == 64 && last_plain < nwa && nw_blk > 1) {
-            atomicOr(&dst[nwa - 1], bswap32(L.stage[nwa - 1]));
-            L.stage[nwa - 1] = 0u;
-        }
+        pack_store_block(L.stage, out + (blk_first_word - word_base) - sh, sh, nw_blk, nwa, run, vec_out, t);
         lds_barrier();
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (a prefetch past the last block: none is issued)
@@ -1136,13 +1058,6 @@ void k_huff_pack_half(const uint8_t *__restrict__ in, uint64_t n, const dc_dtabl
                 uint32_t w4[4] = {blkv[k].x, blkv[k].y, blkv[k].z, blkv[k].w};
                 asm volatile("" : "+v"(w4[0]), "+v"(w4[1]), "+v"(w4[2]), "+v"(w4[3]));
                 const uint32_t rel = (uint32_t)(As - org);
-                auto emit = [&](uint64_t acc, uint32_t nb, uint32_t pos) {
-                    const uint64_t al = acc << ((64u - nb) & 63u);
-                    const uint32_t hi = (uint32_t)(al >> 32), lo = (uint32_t)al, rr = pos & 31u, wi = pos >> 5;
-                    atomicOr(&L.stage[wi], hi >> rr);
-                    atomicOr(&L.stage[wi + 1], __builtin_amdgcn_alignbit(hi, lo, rr));
-                    atomicOr(&L.stage[wi + 2], __builtin_amdgcn_alignbit(lo, 0u, rr));
-                };
                 (void)Tk;
                 uint32_t pos = rel;
 #pragma unroll
@@ -1158,33 +1073,10 @@ void k_huff_pack_half(const uint8_t *__restrict__ in, uint64_t n, const dc_dtabl
                         }
                     }
                     if (!qmode && Th <= 64u) {
-                        emit(acc, Th, pos);
+                        pack_emit(L.stage, acc, Th, pos);
                         pos += Th;
                     } else {   // more than 64 bits (the fold lost its top): the half as two quarters
-                        uint32_t pq = pos;
-#pragma unroll
-                        for (int qq = 0; qq < 2; ++qq) {
-                            uint2 e[4];
-                            uint32_t nq = 0;
-#pragma unroll
-                            for (int i = 0; i < 4; ++i) {
-                                const int bi = 8 * h + 4 * qq + i;
-                                const uint32_t wv = qq ? w4[2 * h + 1] : w4[2 * h];
-                                e[i] = L.tab[(wv >> (8 * (bi & 3))) & 255u];
-                                nq += e[i].y;
-                            }
-                            if (nq <= 64u) {
-                                uint64_t acc = 0;
-#pragma unroll
-                                for (int i = 0; i < 4; ++i) acc = (acc << e[i].y) | e[i].x;
-                                emit(acc, nq, pq);
-                                pq += nq;
-                            } else {
-#pragma unroll
-                                for (int i = 0; i < 4; ++i) { emit(e[i].x, e[i].y, pq); pq += e[i].y; }
-                            }
-                        }
-                        pos = pq;
+                        pos = pack_code_quarters(L.stage, L.tab, w4, h, pos, [](int, uint32_t) {});
                     }
                 }
                 __builtin_amdgcn_sched_barrier(0);
@@ -1196,28 +1088,7 @@ void k_huff_pack_half(const uint8_t *__restrict__ in, uint64_t n, const dc_dtabl
             const uint32_t nwa = shr + nwr;
             const uint32_t last_plain = (R1 & 31) ? nwa - 1 : nwa;   // plain: [shr + 1, last_plain)
             uint32_t *dst = out + (w0 - word_base) - shr;
-            if (vec_out) {
-                const uint32_t nq = last_plain >> 2;
-                for (uint32_t q = 1 + t; q < nq; q += 256) {
-                    uint4 *const sq = reinterpret_cast<uint4 *>(&L.stage[4 * q]);
-                    const uint4 v = *sq;
-                    *sq = make_uint4(0u, 0u, 0u, 0u);
-                    uint4 *const d4 = reinterpret_cast<uint4 *>(dst + 4 * q);
-                    __builtin_nontemporal_store(bswap32(v.x), &d4->x);
-                    __builtin_nontemporal_store(bswap32(v.y), &d4->y);
-                    __builtin_nontemporal_store(bswap32(v.z), &d4->z);
-                    __builtin_nontemporal_store(bswap32(v.w), &d4->w);
-                }
-                const uint32_t hend = last_plain < 4u ? last_plain : 4u;
-                if (t < 4 && (uint32_t)t > shr && (uint32_t)t < hend) { dst[t] = bswap32(L.stage[t]); L.stage[t] = 0u; }
-                const uint32_t tb = nq > 0 ? 4 * nq : 4u;
-                if (t >= 8 && t < 12 && tb + (t - 8) < last_plain) {
-                    dst[tb + (t - 8)] = bswap32(L.stage[tb + (t - 8)]);
-                    L.stage[tb + (t - 8)] = 0u;
-                }
-            } else {
-                for (uint32_t i = t + 1; i < last_plain; i += 256) { dst[i] = bswap32(L.stage[i]); L.stage[i] = 0u; }
-            }
+            pack_store_plain(L.stage, dst, shr, last_plain, vec_out, t);
             if (t == 0 && last_plain > shr) {   // the head word, complete in this round
                 const uint32_t v = bswap32(L.stage[shr]);
                 if (w0 == blk_first_word) atomicOr(&dst[shr], v);
@@ -1361,19 +1232,12 @@ __global__ __launch_bounds__(256) void k_huff_pack_fold(const uint8_t *__restric
                 }
             }
             const uint32_t rel = (uint32_t)(As - org);
-            auto emit = [&](uint64_t a, uint32_t nb, uint32_t pos) {
-                const uint64_t al = a << ((64u - nb) & 63u);
-                const uint32_t hi = (uint32_t)(al >> 32), lo = (uint32_t)al, r = pos & 31u, wi = pos >> 5;
-                atomicOr(&s_stage[wi], hi >> r);
-                atomicOr(&s_stage[wi + 1], __builtin_amdgcn_alignbit(hi, lo, r));
-                atomicOr(&s_stage[wi + 2], __builtin_amdgcn_alignbit(lo, 0u, r));
-            };
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
                 const uint32_t Th = h ? Tk - Hk : Hk;
                 const uint32_t pos = h ? rel + Hk : rel;
                 if (Th <= 64u) {
-                    emit(acc[k][h], Th, pos);
+                    pack_emit(s_stage, acc[k][h], Th, pos);
                 } else {   // the half again, code by code, from its bytes loaded again
                     const uint4 v = (kf == (uint32_t)k) ? rv : LD_PACK(reinterpret_cast<const uint4 *>(in + p));
                     const uint32_t w4[4] = {v.x, v.y, v.z, v.w};
@@ -1381,7 +1245,7 @@ __global__ __launch_bounds__(256) void k_huff_pack_fold(const uint8_t *__restric
 #pragma unroll
                     for (int i = 8 * h; i < 8 * h + 8; ++i) {
                         const uint2 e = s_tab[(w4[i >> 2] >> (8 * (i & 3))) & 255u];
-                        emit(e.x, e.y, pq);
+                        pack_emit(s_stage, e.x, e.y, pq);
                         pq += e.y;
                     }
                 }
@@ -1389,38 +1253,7 @@ __global__ __launch_bounds__(256) void k_huff_pack_fold(const uint8_t *__restric
             __builtin_amdgcn_sched_barrier(0);
         }
         lds_barrier();
-        const uint32_t last_plain = ((run & 31) != 0) ? nwa - 1 : nwa;
-        uint32_t *dst = out + (blk_first_word - word_base) - sh;
-        if (vec_out) {
-            const uint32_t nq = last_plain >> 2;
-            for (uint32_t q = 1 + t; q < nq; q += 256) {
-                uint4 *const sq = reinterpret_cast<uint4 *>(&s_stage[4 * q]);
-                const uint4 v = *sq;
-                *sq = make_uint4(0u, 0u, 0u, 0u);
-                uint4 *const d4 = reinterpret_cast<uint4 *>(dst + 4 * q);
-                __builtin_nontemporal_store(bswap32(v.x), &d4->x);
-                __builtin_nontemporal_store(bswap32(v.y), &d4->y);
-                __builtin_nontemporal_store(bswap32(v.z), &d4->z);
-                __builtin_nontemporal_store(bswap32(v.w), &d4->w);
-            }
-            const uint32_t hend = last_plain < 4u ? last_plain : 4u;
-            if (t < 4 && (uint32_t)t > sh && (uint32_t)t < hend) { dst[t] = bswap32(s_stage[t]); s_stage[t] = 0u; }
-            const uint32_t tb = nq > 0 ? 4 * nq : 4u;
-            if (t >= 8 && t < 12 && tb + (t - 8) < last_plain) {
-                dst[tb + (t - 8)] = bswap32(s_stage[tb + (t - 8)]);
-                s_stage[tb + (t - 8)] = 0u;
-            }
-        } else {
-            for (uint32_t i = t + 1; i < last_plain; i += 256) { dst[i] = bswap32(s_stage[i]); s_stage[i] = 0u; }
-        }
-        if (t == 0) {
-            atomicOr(&dst[sh], bswap32(s_stage[sh]));
-            s_stage[sh] = 0u;
-        }
-        if (t == 64 && last_plain < nwa && nw_blk > 1) {
-            atomicOr(&dst[nwa - 1], bswap32(s_stage[nwa - 1]));
-            s_stage[nwa - 1] = 0u;
-        }
+        pack_store_block(s_stage, out + (blk_first_word - word_base) - sh, sh, nw_blk, nwa, run, vec_out, t);
         lds_barrier();
     }
 }

@@ -1454,6 +1454,8 @@ static __device__ __forceinline__ void lds_barrier()
 #define PACK_BLK_WORDS 9216     /* 36 KiB: a full block of <= 9 bits/symbol is staged whole  */
 #define PACK_PIECES (DC_BLOCK_BYTES / PACK_TILE)
 
+#include "dc_pack_block.inc"
+
 // zero every word two blocks share (plan fallback above PLAN_MAX_WG workgroups of blocks,
 // where k_block_final_wide does not run)
 __global__ void k_zero_bounds(const uint64_t *__restrict__ off, uint64_t nblocks, uint64_t bit_base,
@@ -1574,8 +1576,8 @@ __global__ __launch_bounds__(256) void k_huff_pack(const uint8_t *__restrict__ i
         for (int k = 0; k < (int)(DC_BLOCK_BYTES / PACK_TILE); ++k)
             blkv[k] = LD_PACK(reinterpret_cast<const uint4 *>(in + bb * (uint64_t)DC_BLOCK_BYTES + (uint64_t)k * PACK_TILE + (uint64_t)t * 16));
     };
-    const uint64_t nfull = n / DC_BLOCK_BYTES;
-    if (PF && bx < nfull) load_block(bx);
+    const uint64_t nfull_blk = n / DC_BLOCK_BYTES;   // full blocks (the tile loop's nfull: stage words)
+    if (PF && bx < nfull_blk) load_block(bx);
     for (uint64_t b = bx; b < nblocks; b += gstride) {
         const uint64_t blk_start = b * (uint64_t)DC_BLOCK_BYTES;
         const uint64_t blk_end = (blk_start + DC_BLOCK_BYTES < n) ? blk_start + DC_BLOCK_BYTES : n;
@@ -1610,11 +1612,8 @@ __global__ __launch_bounds__(256) void k_huff_pack(const uint8_t *__restrict__ i
 #pragma unroll
             for (int k = 0; k < PACK_PIECES; ++k) {
                 const uint32_t w4[4] = {blkv[k].x, blkv[k].y, blkv[k].z, blkv[k].w};
-                uint32_t s0 = 0, s1 = 0;
-#pragma unroll
-                for (int i = 0; i < 8; ++i) s0 += s_nb8[(w4[i >> 2] >> (8 * (i & 3))) & 255u];
-#pragma unroll
-                for (int i = 8; i < 16; ++i) s1 += s_nb8[(w4[i >> 2] >> (8 * (i & 3))) & 255u];
+                uint32_t s0, s1;
+                pack_piece_bits(w4, s_nb8, s0, s1);
                 Hk[k] = s0;
                 Tk[k] = s0 + s1;
                 __builtin_amdgcn_sched_barrier(0);
@@ -1655,19 +1654,11 @@ __global__ __launch_bounds__(256) void k_huff_pack(const uint8_t *__restrict__ i
                 // opaque copy: stops the compiler from keeping pass A's lookup addresses live
                 asm volatile("" : "+v"(w4[0]), "+v"(w4[1]), "+v"(w4[2]), "+v"(w4[3]));
                 const uint32_t rel = (uint32_t)(As - org);
-                // OR a right-justified run of nb <= 64 bits into the stage at bit pos (<= 3 words)
-                // Branch-free: the run left-justified in 64 bits has zeros below it, so the
-                // words it does not reach receive 0 (a no-op OR; some lane of a wave needs each
-                // of the 3 ORs anyway, so skipping them per lane saved no LDS cycle and cost
-                // compares and exec-mask branches). nb == 0 only for an all-zero acc (absent
-                // symbols have code 0), where the unmasked shift by 64 & 63 = 0 is harmless.
-                auto emit = [&](uint64_t acc, uint32_t nb, uint32_t pos) {
-                    const uint64_t al = acc << ((64u - nb) & 63u);
-                    const uint32_t hi = (uint32_t)(al >> 32), lo = (uint32_t)al, r = pos & 31u, wi = pos >> 5;
-                    atomicOr(&s_stage[wi], hi >> r);
-                    atomicOr(&s_stage[wi + 1], __builtin_amdgcn_alignbit(hi, lo, r));
-                    atomicOr(&s_stage[wi + 2], __builtin_amdgcn_alignbit(lo, 0u, r));
-                };
+                // pack_code_piece's body, kept as this kernel's own text around pack_emit: as a
+                // call the same lines compile to another block layout here (the half / quarter
+                // branch the other way round), and the C4 pack, all quarter mode, measured ~1%
+                // slower than this text (profiles/pack_shared_body_ab.log)
+                auto emit = [&](uint64_t acc, uint32_t nb, uint32_t pos) { pack_emit(s_stage, acc, nb, pos); };
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {
                     const uint32_t Th = h ? Tk[k] - Hk[k] : Hk[k];
@@ -1711,54 +1702,12 @@ __global__ __launch_bounds__(256) void k_huff_pack(const uint8_t *__restrict__ i
                         }
                     }
                 }
-                if (PF && bnext < nfull)   // piece k of the next block, in flight through the rest
+                if (PF && bnext < nfull_blk)   // piece k of the next block, in flight through the rest
                     blkv[k] = LD_PACK(reinterpret_cast<const uint4 *>(in + bnext * (uint64_t)DC_BLOCK_BYTES + (uint64_t)k * PACK_TILE + (uint64_t)t * 16));
                 __builtin_amdgcn_sched_barrier(0);   // keep the pieces' lookups from being hoisted
             }
             lds_barrier();
-            // stage word sh = the block's first word, shared with the previous block; the last
-            // word is shared with the next one when the block ends inside it: those two are
-            // OR-ed into HBM by one lane each, the rest are plain stores (uint4 where whole)
-            const uint32_t last_plain = ((run & 31) != 0) ? nwa - 1 : nwa;   // plain: [sh+1, last_plain)
-            uint32_t *dst = out + (blk_first_word - word_base) - sh;
-            // every stage word read below is zeroed by the thread that read it (the stage is
-            // zero at the next block's start; words < sh and past nwa were never written)
-            if (vec_out) {
-                const uint32_t nq = last_plain >> 2;   // uint4 q covers stage words [4q, 4q+4)
-                for (uint32_t q = 1 + t; q < nq; q += 256) {
-                    uint4 *const sq = reinterpret_cast<uint4 *>(&s_stage[4 * q]);
-                    const uint4 v = *sq;
-                    *sq = make_uint4(0u, 0u, 0u, 0u);
-                    // streaming (nt) stores: same-box A/B on 1 GiB C2, pack 0.420 -> 0.382 ms
-                    // (the decode after it reads the payload no slower)
-                    uint4 *const d4 = reinterpret_cast<uint4 *>(dst + 4 * q);
-                    __builtin_nontemporal_store(bswap32(v.x), &d4->x);
-                    __builtin_nontemporal_store(bswap32(v.y), &d4->y);
-                    __builtin_nontemporal_store(bswap32(v.z), &d4->z);
-                    __builtin_nontemporal_store(bswap32(v.w), &d4->w);
-                }
-                // head: words sh+1..3 of uint4 0; tail: words of the last, partial uint4
-                const uint32_t hend = last_plain < 4u ? last_plain : 4u;
-                if (t < 4 && (uint32_t)t > sh && (uint32_t)t < hend) { dst[t] = bswap32(s_stage[t]); s_stage[t] = 0u; }
-                const uint32_t tb = nq > 0 ? 4 * nq : 4u;
-                if (t >= 8 && t < 12 && tb + (t - 8) < last_plain) {
-                    dst[tb + (t - 8)] = bswap32(s_stage[tb + (t - 8)]);
-                    s_stage[tb + (t - 8)] = 0u;
-                }
-            } else {
-                for (uint32_t i = t + 1; i < last_plain; i += 256) { dst[i] = bswap32(s_stage[i]); s_stage[i] = 0u; }
-            }
-            // the first word (shared with the previous block when the block starts inside it)
-            // and the last (shared with the next one when the block ends inside it) are
-            // OR-ed into HBM, where k_block_final_wide zeroed them (no-return atomics)
-            if (t == 0) {
-                atomicOr(&dst[sh], bswap32(s_stage[sh]));
-                s_stage[sh] = 0u;
-            }
-            if (t == 64 && last_plain < nwa && nw_blk > 1) {
-                atomicOr(&dst[nwa - 1], bswap32(s_stage[nwa - 1]));
-                s_stage[nwa - 1] = 0u;
-            }
+            pack_store_block(s_stage, out + (blk_first_word - word_base) - sh, sh, nw_blk, nwa, run, vec_out, t);
             lds_barrier();
             continue;
         }
@@ -1846,7 +1795,7 @@ __global__ __launch_bounds__(256) void k_huff_pack(const uint8_t *__restrict__ i
         for (uint32_t i = 4u * t; i < PACK_BLK_WORDS + 4; i += 1024u)
             *reinterpret_cast<uint4 *>(&s_stage[i]) = make_uint4(0u, 0u, 0u, 0u);
         __syncthreads();
-        if (PF && bnext < nfull) load_block(bnext);
+        if (PF && bnext < nfull_blk) load_block(bnext);
     }
 }
 
@@ -2039,11 +1988,8 @@ __global__ __launch_bounds__(256) void k_fe_pack(const uint8_t *__restrict__ in,
                 w4[q] = (w4[q] & ~m8) | (Z4 & m8) | sec;
             }
             blkv[k] = make_uint4(w4[0], w4[1], w4[2], w4[3]);
-            uint32_t s0 = 0, s1 = 0;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) s0 += s_nb8[(w4[i >> 2] >> (8 * (i & 3))) & 255u];
-#pragma unroll
-            for (int i = 8; i < 16; ++i) s1 += s_nb8[(w4[i >> 2] >> (8 * (i & 3))) & 255u];
+            uint32_t s0, s1;
+            pack_piece_bits(w4, s_nb8, s0, s1);
             Pk[k] = (s0 + s1) | ((16u - nul) << 18) | (s0 << 23);
             // materialised here: sunk to the scan, the sums kept every piece's 16 lookups live
             asm volatile("" : "+v"(Pk[k]));
@@ -2058,18 +2004,11 @@ __global__ __launch_bounds__(256) void k_fe_pack(const uint8_t *__restrict__ in,
         }
         lds_barrier();
         const uint64_t org = (blk_first_word - sh) << 5;   // absolute bit of stage bit 0
-        auto emit = [&](uint64_t acc, uint32_t nb, uint32_t pos) {   // as in k_huff_pack
-            const uint64_t al = acc << ((64u - nb) & 63u);
-            const uint32_t hi = (uint32_t)(al >> 32), lo = (uint32_t)al, r = pos & 31u, wi = pos >> 5;
-            atomicOr(&s_stage[wi], hi >> r);
-            atomicOr(&s_stage[wi + 1], __builtin_amdgcn_alignbit(hi, lo, r));
-            atomicOr(&s_stage[wi + 2], __builtin_amdgcn_alignbit(lo, 0u, r));
-        };
         uint64_t run = blk_abs, mrun = m0;
         if (b == 0 && fc.first) {   // M[0] = the type byte 8 (EIGHT_BIT_PRUNED, small_compression.c:39), chunk 0's start
             const uint2 h = s_tab[8];
             if (t == 0) {
-                emit(h.x, h.y, (uint32_t)(blk_abs - org));
+                pack_emit(s_stage, h.x, h.y, (uint32_t)(blk_abs - org));
                 s_cb[0] = 0u;
                 if (SH) s_cbg[0] = 0u;   // (the first shard: global = local)
             }
@@ -2109,46 +2048,7 @@ __global__ __launch_bounds__(256) void k_fe_pack(const uint8_t *__restrict__ in,
             uint32_t w4[4] = {blkv[k].x, blkv[k].y, blkv[k].z, blkv[k].w};
             asm volatile("" : "+v"(w4[0]), "+v"(w4[1]), "+v"(w4[2]), "+v"(w4[3]));
             const uint32_t rel = (uint32_t)(As - org);
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const uint32_t Th = h ? Tk - Hk : Hk;
-                const uint32_t pos = h ? rel + Hk : rel;
-                if (!qmode && Th <= 64u) {
-                    uint64_t acc = 0;
-#pragma unroll
-                    for (int i = 8 * h; i < 8 * h + 8; ++i) {
-                        const uint2 e = s_tab[(w4[i >> 2] >> (8 * (i & 3))) & 255u];
-                        acc = (acc << e.y) | e.x;
-                        tally(i, e.y);
-                    }
-                    emit(acc, Th, pos);
-                } else {
-                    uint32_t pq = pos;
-#pragma unroll
-                    for (int qq = 0; qq < 2; ++qq) {
-                        uint2 e[4];
-                        uint32_t nq = 0;
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) {
-                            const int bi = 8 * h + 4 * qq + i;
-                            const uint32_t wv = qq ? w4[2 * h + 1] : w4[2 * h];
-                            e[i] = s_tab[(wv >> (8 * (bi & 3))) & 255u];
-                            nq += e[i].y;
-                            tally(bi, e[i].y);
-                        }
-                        if (nq <= 64u) {
-                            uint64_t acc = 0;
-#pragma unroll
-                            for (int i = 0; i < 4; ++i) acc = (acc << e[i].y) | e[i].x;
-                            emit(acc, nq, pq);
-                            pq += nq;
-                        } else {
-#pragma unroll
-                            for (int i = 0; i < 4; ++i) { emit(e[i].x, e[i].y, pq); pq += e[i].y; }
-                        }
-                    }
-                }
-            }
+            pack_code_piece(s_stage, s_tab, w4, qmode, Hk, Tk, rel, tally);
             uint32_t cap, capg = 0;   // bits before the chunk starts
             fe_chunk_bits<SH>(L4, jj, jjg, cap, capg);
             if (has) s_cb[(uint32_t)(((mi + j0) >> slog) - cf)] = (uint32_t)(As - blk_abs) + cap;
@@ -2156,42 +2056,7 @@ __global__ __launch_bounds__(256) void k_fe_pack(const uint8_t *__restrict__ in,
             __builtin_amdgcn_sched_barrier(0);
         }
         lds_barrier();
-        // ---- store phase: as in k_huff_pack ----
-        const uint32_t last_plain = ((run & 31) != 0) ? nwa - 1 : nwa;
-        uint32_t *dst = out + (blk_first_word - word_base) - sh;
-        if (vec_out) {
-            const uint32_t nq = last_plain >> 2;
-            for (uint32_t q = 1 + t; q < nq; q += 256) {
-                uint4 *const sq = reinterpret_cast<uint4 *>(&s_stage[4 * q]);
-                const uint4 v = *sq;
-                *sq = make_uint4(0u, 0u, 0u, 0u);
-                uint4 *const d4 = reinterpret_cast<uint4 *>(dst + 4 * q);
-                __builtin_nontemporal_store(bswap32(v.x), &d4->x);
-                __builtin_nontemporal_store(bswap32(v.y), &d4->y);
-                __builtin_nontemporal_store(bswap32(v.z), &d4->z);
-                __builtin_nontemporal_store(bswap32(v.w), &d4->w);
-            }
-            const uint32_t hend = last_plain < 4u ? last_plain : 4u;
-            if (t < 4 && (uint32_t)t > sh && (uint32_t)t < hend) { dst[t] = bswap32(s_stage[t]); s_stage[t] = 0u; }
-            const uint32_t tb = nq > 0 ? 4 * nq : 4u;
-            if (t >= 8 && t < 12 && tb + (t - 8) < last_plain) {
-                dst[tb + (t - 8)] = bswap32(s_stage[tb + (t - 8)]);
-                s_stage[tb + (t - 8)] = 0u;
-            }
-        } else {
-            for (uint32_t i = t + 1; i < last_plain; i += 256) { dst[i] = bswap32(s_stage[i]); s_stage[i] = 0u; }
-        }
-        // (nw_blk = 0: a shard's one-byte last block, a pair's start, on a word boundary. It has
-        // no word: its first word would be the one at index = the stream's words, which words_cap
-        // need not hold)
-        if (t == 0 && nw_blk > 0) {
-            atomicOr(&dst[sh], bswap32(s_stage[sh]));
-            s_stage[sh] = 0u;
-        }
-        if (t == 64 && last_plain < nwa && nw_blk > 1) {
-            atomicOr(&dst[nwa - 1], bswap32(s_stage[nwa - 1]));
-            s_stage[nwa - 1] = 0u;
-        }
+        pack_store_block(s_stage, out + (blk_first_word - word_base) - sh, sh, nw_blk, nwa, run, vec_out, t);
         // ---- the sync index: chunk lengths from consecutive starts; group bases ----
         if (sync_len != nullptr) {
             const uint64_t hd = m0 > 0 ? ((m0 - 1) >> slog) >> 1 : ~0ull, td = ct >> 1;

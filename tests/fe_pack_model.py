@@ -25,23 +25,16 @@ import numpy as np
 from oracle import oracle as orc
 from tests import huff_decode_model as D
 from tests import small_frontend_model as F
+from tests.pack_block_model import (BLOCK, GROUP, PIECE, PIECES, PLAN_WG_BLOCKS,  # noqa: F401 (the tests')
+                                    seq_layout, store_cuts, words_touched)
+from tests.pack_block_model import PACK_BLK_WORDS as STAGE
 
-BLOCK = 32768               # DC_BLOCK_BYTES
-PIECE = 4096                # PACK_TILE: 256 lanes x 16 bytes
-PIECES = BLOCK // PIECE
-STAGE = 9216                # PACK_BLK_WORDS
-GROUP = 64                  # DC_SYNC_GROUP
-PLAN_WG_BLOCKS = 64
 SPACE = 0x20
 SYNCS = (16, 32, 64, 256, 1024)
 DC_E_ARG, DC_E_STATE, DC_E_FALLBACK = -1, -5, -8
 LEN_POISON = 0x5A5A
 
 words_needed = D.words_needed
-
-
-def words_touched(bit_base, bits):
-    return ((bit_base & 31) + bits + 31) >> 5
 
 
 def _u8(x):
@@ -212,8 +205,8 @@ def stitch(parts):
 def geometry(x, ctx, lengths, n_ary, S, k=1, shift=0, grid=0, guard=True):
     """k_fe_pack's cuts for the input x: k = 1 the whole-stream call, 2 the shard call; shift: words
     from a 16-byte boundary to d_words; grid: DC_OPT_PACK_GRID; guard: thread 0's OR of the block's
-    first word only when the block has a word. The flag is a hand-kept restatement of k_fe_pack's
-    `if (t == 0 && nw_blk > 0)` in dc_core.hip (False: that line without `nw_blk > 0`): nothing ties
+    first word only when the block has a word. The flag is a hand-kept restatement of pack_store_block's
+    `if (t == 0 && nw_blk > 0)` in dc_pack_block.inc (False: that line without `nw_blk > 0`): nothing ties
     it to the source, and an OR of zero shows in no byte, so what the tests assert from it is a
     property of the model and of the catalogue, not a check of the kernel."""
     bit, sym, lb, rb = ctx
@@ -259,13 +252,7 @@ def geometry(x, ctx, lengths, n_ary, S, k=1, shift=0, grid=0, guard=True):
             touched.add(w0)                       # thread 0's OR of the block's first word
         r["words"] = (w0, w0 + nw_blk)
         r["past_end"] = sorted(w for w in touched if w >= nwords)
-        nwa = sh + nw_blk
-        last_plain = nwa - 1 if (blk_abs + s_bits) & 31 else nwa
-        r.update(nwa=nwa, last_plain=last_plain, last_or=last_plain < nwa and nw_blk > 1)
-        if vec_out:
-            nq = last_plain >> 2
-            tb = 4 * nq if nq > 0 else 4
-            r.update(nq=nq, head=max(0, min(last_plain, 4) - sh - 1), tail=max(0, last_plain - tb))
+        r.update(store_cuts(sh, nw_blk, r["ends_on_word"], vec_out))
         # the chunks: local (M = 0) and, for a shard, global
         for pre, M in (("", 0),) + ((("g", sym),) if k == 2 else ()):
             cf = (M + m0 + S - 1) >> slog
@@ -643,24 +630,9 @@ SEQS = {
 SEQ_S = 64      # (lim = 9216 - 2 * 514 - 4 words: every block of 5-bit codes fits)
 
 
-def seq_layout(steps, grid):
-    """([block positions of each run of steps inside one workgroup], blocks in all). Block 0 is a
-    filler: its sh is 0 by definition. Under grid g a workgroup runs blocks b, b + g, b + 2 g ..; by
-    default (a block pair per workgroup, G = blocks / 2 workgroups) it runs b and b + G, so a sequence
-    of three reaches it as its two pairs."""
-    if grid == 0:
-        runs = len(steps) - 1
-        return [[2 * j + 1, 2 * j + 1 + 2 * runs] for j in range(runs)], 4 * runs
-    return [[1 + i * grid for i in range(len(steps))]], (len(steps) - 1) * grid + 2
-
-
 def seq_runs(name, grid):
-    """[(block positions, the steps they hold)] of a planted seq case"""
-    steps = SEQS[name]
-    pos, nblocks = seq_layout(steps, grid)
-    if grid == 0:
-        return [(ps, steps[j: j + 2]) for j, ps in enumerate(pos)], nblocks
-    return [(pos[0], steps)], nblocks
+    """[(block positions, the steps they hold)] of a planted seq case, blocks in all"""
+    return seq_layout(SEQS[name], grid)
 
 
 def _seq_planted(name, grid):

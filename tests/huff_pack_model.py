@@ -24,22 +24,14 @@ import numpy as np
 
 from oracle import oracle as orc
 from tests import huff_decode_model as D
+from tests.pack_block_model import (BLOCK, GROUP, PACK_BLK_WORDS, PIECES, PLAN_WG_BLOCKS,  # noqa: F401 (the tests')
+                                    seq_layout, store_cuts, words_touched)
+from tests.pack_block_model import PIECE as TILE
 
-BLOCK = 32768               # DC_BLOCK_BYTES
-TILE = 4096                 # PACK_TILE: 256 lanes x 16 bytes
-PIECES = BLOCK // TILE
-PACK_BLK_WORDS = 9216       # the fast path's stage: 9 bits per symbol exactly
-GROUP = 64                  # DC_SYNC_GROUP
-PLAN_WG_BLOCKS = 64         # blocks per workgroup of k_block_local / k_block_final_wide
 SYNCS = (16, 32, 64, 128, 256, 512, 1024)
 DC_E_ARG, DC_E_NOCODE, DC_E_STATE, DC_E_CAPACITY = -1, -4, -5, -6
 
 words_needed = D.words_needed
-
-
-def words_touched(bit_base, bits):
-    """words that hold a bit of the stream (dc_huff_words_needed without its slack)"""
-    return ((bit_base & 31) + bits + 31) >> 5
 
 
 # ---- tables ----------------------------------------------------------------------------------
@@ -135,13 +127,7 @@ def pack_geometry(x, nbits, bit_base=0, out_word_shift=0, S=64, grid=0, detail=T
              "sync": None if path == "fixed8" else "xor" if path == "slow" else
              "one" if cm == 1 else "dpp" if cm == 4 else "shfl"}
         if path == "fast":
-            nwa = sh + nw_blk
-            last_plain = nwa if run & 31 == 0 else nwa - 1
-            r.update(nwa=nwa, last_plain=last_plain, last_or=last_plain < nwa and nw_blk > 1)
-            if vec_out:
-                nq = last_plain >> 2
-                tb = 4 * nq if nq > 0 else 4
-                r.update(nq=nq, head=max(0, min(last_plain, 4) - sh - 1), tail=max(0, last_plain - tb))
+            r.update(store_cuts(sh, nw_blk, run & 31 == 0, vec_out))
             if detail:
                 s8 = sb[lo:hi].reshape(PIECES, 256, 2, 2, 4)     # piece, lane, half, quarter, code
                 Q = s8.sum(axis=-1)
@@ -359,23 +345,10 @@ SEQS = {
 SEQ_GRIDS = (1, 2, 0)
 
 
-def seq_layout(steps, grid):
-    """[(block positions of a run of steps inside one workgroup)], blocks in all. By default a
-    workgroup runs two blocks, so a sequence of three reaches it as its two pairs."""
-    if grid == 0:
-        runs = [steps[i: i + 2] for i in range(len(steps) - 1)]
-        g = 2 * len(runs)
-        pos = [[2 * j + 1, 2 * j + 1 + g] for j in range(len(runs))]
-    else:
-        runs, pos = [steps], [[1 + i * grid for i in range(len(steps))]]
-    return runs, pos, max(p[-1] for p in pos) + 1
-
-
 def _seq_case(name, grid):
-    steps = SEQS[name]
-    runs, pos, nblocks = seq_layout(steps, grid)
+    runs, nblocks = seq_layout(SEQS[name], grid)
     want = {}
-    for r, ps in zip(runs, pos):
+    for ps, r in runs:
         want.update(dict(zip(ps, r)))
     parts, cum = [], 0
     for b in range(nblocks):
@@ -395,7 +368,7 @@ def _seq_case(name, grid):
 def seq_blocks(case):
     """[(block positions of each run)] of a seq case"""
     name = case.name[4: case.name.rindex("-grid")]
-    return seq_layout(SEQS[name], case.grid)[1]
+    return [ps for ps, _ in seq_layout(SEQS[name], case.grid)[0]]
 
 
 # ---- stores ----------------------------------------------------------------------------------
