@@ -36,7 +36,8 @@ class HBatch(C.Structure):
 
 class DcError(RuntimeError):
     NAMES = {-1: "DC_E_ARG", -2: "DC_E_HIP", -3: "DC_E_CODE_TOO_LONG", -4: "DC_E_NOCODE",
-             -5: "DC_E_STATE", -6: "DC_E_CAPACITY", -7: "DC_E_STREAM", -8: "DC_E_FALLBACK"}
+             -5: "DC_E_STATE", -6: "DC_E_CAPACITY", -7: "DC_E_STREAM", -8: "DC_E_FALLBACK",
+             -9: "DC_E_CHECKSUM"}
 
     def __init__(self, fn, rc):
         super().__init__(f"{fn} failed: {self.NAMES.get(rc, rc)}")
@@ -172,6 +173,11 @@ def _declare_core(L):
         "dc_small_batch_bound": ([u64, u64], u64),
         "dc_small_compress_batch": ([vp, P, P, u64, P, u64, P, P], i32),
         "dc_small_decompress_batch": ([vp, P, P, u64, P, P, u64, P], i32),
+        "dc_crc32_host": ([u32, vp, C.c_size_t], u32),
+        "dc_crc32_combine": ([u32, u32, u64], u32),
+        "dc_crc32": ([vp, P, u64, P], i32),
+        "dc_crc32_batch": ([vp, P, u64, P, P, u64, P, P], i32),
+        "dc_crc32_verify_batch": ([vp, P, u64, P, P, u64, P, P], i32),
         "dc_small_compress_body": ([vp, P, u64, i32, u64, P, C.POINTER(u64)], i32),
         "dc_small_compress_body_plan": ([vp, P, u64, i32, u64, C.POINTER(u64)], i32),
         "dc_small_compress_body_write": ([vp, P, u64, i32, u64, P, C.POINTER(u64)], i32),

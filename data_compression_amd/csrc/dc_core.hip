@@ -22,6 +22,7 @@
 #include "dc_small_batch_bound.h"
 #include "dc_batch_range.h"
 #include "dc_huff_limit.h"
+#include "dc_crc32.h"
 
 #define DC_VERSION "dc-mi355x 0.1 (gfx950)"
 #define DC_SYNC_GROUP 64
@@ -6265,6 +6266,7 @@ __global__ __launch_bounds__(256) void k_copy_probe(const uint4 *__restrict__ sr
 #include "dc_batch_range_kernels.inc"
 #include "dc_nyb_batch_kernels.inc"
 #include "dc_small_batch_kernels.inc"
+#include "dc_crc_kernels.inc"
 
 #ifdef DC_AB_KERNELS
 #include "dc_ab_kernels.inc"
@@ -6298,6 +6300,8 @@ struct dc_ctx {
     uint64_t last_groups;                         // groups of the last S = 64 decode (redo mask length)
     uint64_t *d_rng;        size_t rng_cap;       // range decode: items per range, then their offsets (+ total)
     uint64_t *d_hb;         size_t hb_cap;        // batch codec: first failure, then payload bytes and chunks per segment
+    uint32_t *d_crct;                             // checksums: the lookup tables (CRC_T_WORDS, written once at create)
+    uint32_t *d_crcp;       size_t crcp_cap;      // checksums: dc_crc32's weighted piece CRCs
     uint64_t *d_hloc;                             // this context's last histogram (256 u64; hist[] may be all-reduced)
     const dc_dtable *plan_table;                  // the table and device total of the last plan
     uint64_t *plan_total;
@@ -6401,6 +6405,17 @@ static void t_end(dc_ctx *c, int slot)
 
 static int g_rank_uploaded = -1;
 
+// the checksum kernels' tables, made once a process (dc_crc_kernels.inc: CRC_T_*)
+static const uint32_t *crc_host_tables()
+{
+    struct Tabs {
+        uint32_t w[CRC_T_WORDS];
+        Tabs() { crc_make_tables(w); }
+    };
+    static const Tabs t;
+    return t.w;
+}
+
 extern "C" {
 
 const char *dc_version(void) { return DC_VERSION; }
@@ -6446,6 +6461,11 @@ static int ctx_create(dc_ctx **out, int device, void *stream, bool own)
         free(c);
         return DC_E_HIP;
     }
+    if (hipMalloc((void **)&c->d_crct, CRC_T_WORDS * sizeof(uint32_t)) != hipSuccess ||
+        hipMemcpy(c->d_crct, crc_host_tables(), CRC_T_WORDS * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) {
+        free(c);
+        return DC_E_HIP;
+    }
     c->opt_d8_static = D8_STATIC_PCT;
     {   // A/B knobs (environment; tools/kern_ab.py sets the same options per context), read once and clamped
         const char *e;
@@ -6485,6 +6505,8 @@ void dc_ctx_destroy(dc_ctx *c)
     if (c->d_fixpos) (void)hipFree(c->d_fixpos);
     if (c->d_rng) (void)hipFree(c->d_rng);
     if (c->d_hb) (void)hipFree(c->d_hb);
+    if (c->d_crct) (void)hipFree(c->d_crct);
+    if (c->d_crcp) (void)hipFree(c->d_crcp);
     if (c->d_scr) (void)hipFree(c->d_scr);
     if (c->d_meta) (void)hipFree(c->d_meta);
     if (c->d_summ) (void)hipFree(c->d_summ);
@@ -8079,6 +8101,64 @@ int dc_small_decompress_batch(dc_ctx *c, const uint8_t *d_in, const uint64_t *d_
     const uint64_t grid = hbatch_grid(c, (count + SB_WAVES - 1) / SB_WAVES, 2048);
     LAUNCH(c, "small_batch_dec", k_small_batch_dec, grid, SB_THREADS, d_in, d_in_off, d_out_off, count, d_out, out_cap,
            d_status, first);
+    return DC_OK;
+}
+
+// ---- checksums (dc_crc_kernels.inc, dc_crc32.h) -----------------------------------------
+uint32_t dc_crc32_host(uint32_t crc, const void *data, size_t n)
+{
+    if (!data || n == 0) return crc;
+    return dc_crc32_update_tables(reinterpret_cast<const uint32_t(*)[256]>(crc_host_tables() + CRC_T_SL), crc,
+                                  (const uint8_t *)data, n);
+}
+
+uint32_t dc_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b) { return dc_crc32_combine_calc(crc_a, crc_b, len_b); }
+
+int dc_crc32(dc_ctx *c, const uint8_t *d_in, uint64_t n, uint32_t *d_crc)
+{
+    if (!c || !d_crc || (n && !d_in)) return DC_E_ARG;
+    if (n == 0) {
+        HIPCHK(hipMemsetAsync(d_crc, 0, sizeof(uint32_t), c->stream));
+        return DC_OK;
+    }
+    const uint64_t np = (n - 1) / DC_CRC_PIECE + 1;
+    if (ensure((void **)&c->d_crcp, &c->crcp_cap, np * sizeof(uint32_t))) return DC_E_HIP;
+    const uint64_t grid = hbatch_grid(c, (np + CRC_WAVES - 1) / CRC_WAVES, 2048);   // a wave per piece, 8 workgroups per CU
+    LAUNCH(c, "crc_pieces", k_crc_pieces, grid, CRC_THREADS, d_in, n, np, c->d_crcp, (const uint32_t *)c->d_crct);
+    LAUNCH(c, "crc_fold", k_crc_fold, 1, 1024, (const uint32_t *)c->d_crcp, np, d_crc);
+    return DC_OK;
+}
+
+// What the two batch calls begin with: 1 (nothing to do), 0 with the first-failure slot turned
+// over, or an error.
+static int crc_batch_begin(dc_ctx *c, const uint8_t *d_in, const uint64_t *d_beg, const uint64_t *d_end, uint64_t count,
+                           const uint32_t *d_crc, const int32_t *d_status, unsigned long long **first)
+{
+    if (!c) return DC_E_ARG;
+    if (count == 0) return 1;
+    if (count > DC_RANGES_MAX || !d_in || !d_beg || !d_end || !d_crc || !d_status) return DC_E_ARG;
+    return hbatch_begin(c, 0, first);
+}
+
+int dc_crc32_batch(dc_ctx *c, const uint8_t *d_in, uint64_t in_cap, const uint64_t *d_beg, const uint64_t *d_end,
+                   uint64_t count, uint32_t *d_crc, int32_t *d_status)
+{
+    unsigned long long *first;
+    if (const int r = crc_batch_begin(c, d_in, d_beg, d_end, count, d_crc, d_status, &first)) return r > 0 ? DC_OK : r;
+    const uint64_t grid = hbatch_grid(c, (count + CRC_WAVES - 1) / CRC_WAVES, 2048);   // a wave per buffer, 8 workgroups per CU
+    LAUNCH(c, "crc_batch", k_crc_batch<false>, grid, CRC_THREADS, d_in, in_cap, d_beg, d_end, count,
+           (const uint32_t *)nullptr, d_crc, d_status, first, (const uint32_t *)c->d_crct);
+    return DC_OK;
+}
+
+int dc_crc32_verify_batch(dc_ctx *c, const uint8_t *d_in, uint64_t in_cap, const uint64_t *d_beg, const uint64_t *d_end,
+                          uint64_t count, const uint32_t *d_expect, int32_t *d_status)
+{
+    unsigned long long *first;
+    if (const int r = crc_batch_begin(c, d_in, d_beg, d_end, count, d_expect, d_status, &first)) return r > 0 ? DC_OK : r;
+    const uint64_t grid = hbatch_grid(c, (count + CRC_WAVES - 1) / CRC_WAVES, 2048);
+    LAUNCH(c, "crc_verify", k_crc_batch<true>, grid, CRC_THREADS, d_in, in_cap, d_beg, d_end, count, d_expect,
+           (uint32_t *)nullptr, d_status, first, (const uint32_t *)c->d_crct);
     return DC_OK;
 }
 

@@ -405,7 +405,9 @@ class Codec:
         length asked for must be the stream's). Asynchronous, one launch, no host read unless
         `out` is left to default, which reads out_off[-1] once to size it. Returns device tensors
         (out, status); a stream of any status but 0 writes no byte, and no byte outside the asked
-        ranges is written."""
+        ranges is written. A damaged letter byte still decodes to its length with status 0:
+        crc32_verify_batch(out, crc, status, offsets=out_off), with the crc32_batch of the inputs
+        taken at encode, turns such a buffer into DC_E_CHECKSUM."""
         return self._stream_decompress_batch("small_decompress_batch_into", self.L.dc_small_decompress_batch, (), data,
                                              offsets, out_off, out)
 
@@ -481,7 +483,9 @@ class Codec:
         out: an optional preallocated uint8 buffer (else nyb_batch_bound(x.numel(), count) bytes);
         out_cap: a smaller capacity to hand to the kernels. Returns device tensors (out, out_off,
         status): out_off (int64, count + 1) always holds the true stream offsets, status (int32)
-        each buffer's outcome; batch_status() gives the lowest failing buffer's."""
+        each buffer's outcome; batch_status() gives the lowest failing buffer's.
+        The streams carry no checksum: keep crc32_batch(x, offsets=offsets)[0] beside them and
+        hand it, with the decode's status, to crc32_verify_batch after nyb_decompress_batch_into."""
         return self._stream_compress_batch("nyb_compress_batch", self.L.dc_nyb_compress_batch, self.nyb_batch_bound,
                                            (int(bool(modify)),), x, offsets, out, out_cap)
 
@@ -499,7 +503,10 @@ class Codec:
         length asked for must be the stream's). Asynchronous, one launch, no host read unless
         `out` is left to default, which reads out_off[-1] once to size it. Returns device tensors
         (out, status); a failed stream's own range holds unspecified bytes, and no byte outside
-        the asked ranges is written."""
+        the asked ranges is written. A damaged literal byte still decodes to its length with
+        status 0: crc32_verify_batch(out, crc, status, offsets=out_off), with the crc32_batch of
+        the inputs taken at encode, turns such a buffer into DC_E_CHECKSUM (and skips the streams
+        that failed here)."""
         return self._stream_decompress_batch("nyb_decompress_batch_into", self.L.dc_nyb_decompress_batch_async,
                                              (int(bool(modify)),), data, offsets, out_off, out)
 
@@ -722,7 +729,7 @@ class Codec:
         return v
 
     def encode_batch(self, x, offsets, n_ary: int = 2, sync_syms: int = 64, payload=None, sync_len=None,
-                     payload_cap=None, sync_cap=None, table=None, max_bits=None):
+                     payload_cap=None, sync_cap=None, table=None, max_bits=None, checksum: bool = False):
         """dc_huff_encode_batch: segment i = x[offsets[i]:offsets[i+1]] (device uint8 x, int64
         offsets of count + 1 entries, any alignment, each segment <= 65536 bytes) coded under a
         table of its own, or stored when that is not smaller. Asynchronous, no host read; the
@@ -737,7 +744,11 @@ class Codec:
         max_bits (own tables only): no code of any segment's table longer than that many bits
         (dc_huff_encode_batch_limit); a segment with more distinct bytes than such codes is
         stored under a record of zeros. With table=, the cap belongs to batch_table(): a
-        ValueError. The result carries "max_bits"."""
+        ValueError. The result carries "max_bits".
+        checksum (any mode): the result also carries "crc", the CRC-32 of every input segment
+        (crc32_batch over the same offsets: one more launch), for decode_batch(verify=True). A
+        segment whose offsets decrease has crc 0 and fails the encode anyway. The default
+        leaves the call and its result exactly as they are without it."""
         if x.dtype != torch.uint8 or not x.is_contiguous():
             raise ValueError("encode_batch input: contiguous uint8")
         if table is not None and max_bits is not None:
@@ -756,6 +767,8 @@ class Codec:
                "status": self._t(max(count, 1), torch.int32)[:count], "max_bits": max_bits}
         b = self._hbatch(enc, payload_cap, sync_cap)
         enc["payload_cap"], enc["sync_cap"] = int(b.payload_cap), int(b.sync_cap)
+        if checksum:   # (before the encode: batch_status() after the call is the encode's)
+            enc["crc"] = self.crc32_batch(x, offsets=offsets)[0]
         if table is not None:
             enc["table"] = table
             check("dc_huff_encode_batch_shared",
@@ -771,19 +784,28 @@ class Codec:
     def encode_blocks(self, x, block: int = 65536, **kw):
         """encode_batch of x cut into independent blocks of `block` bytes (the last shorter),
         a table each: the reference's own block design (n_ary_huffman.c:1210-1255); with
-        table=..., all under that one table; with max_bits=..., each table capped."""
+        table=..., all under that one table; with max_bits=..., each table capped; with
+        checksum=True, the CRC-32 of every block in "crc"."""
         if not 0 < block <= self.SEG_MAX:
             raise ValueError("encode_blocks: 0 < block <= 65536")
         return self.encode_batch(x, self._block_offsets(x, block), **kw)
 
-    def decode_batch(self, enc, out=None, out_off=None):
+    def decode_batch(self, enc, out=None, out_off=None, verify: bool = False):
         """dc_huff_decode_batch of the dict encode_batch returned. out_off (int64 device tensor
         or sequence): count + 1 entries put segment i at out[out_off[i]:out_off[i+1]]; count
         entries give each segment's start alone (its length is the encoded segment's), so the
         outputs may lie anywhere in out (dc_huff_decode_batch_scatter). Default: the segments
         back to back from 0. Asynchronous; returns (out, out_off). Per-segment outcome in
         enc["status"], the first failure by batch_status(). A batch encoded under a shared
-        table (enc["table"]) is decoded under it (dc_huff_decode_batch_shared)."""
+        table (enc["table"]) is decoded under it (dc_huff_decode_batch_shared).
+        verify: after the decode, the CRC-32 of every decoded segment against enc["crc"]
+        (encode_batch(checksum=True); a ValueError without it), in either layout: a segment that
+        decoded with DC_OK to other bytes than went in (a damaged stored segment, a code
+        swapped for another of its length, a wrong table) becomes DC_E_CHECKSUM (-9) in
+        enc["status"], and batch_status() answers for the decode and the verify together. One
+        more launch (crc32_verify_batch); segments that failed the decode are not read."""
+        if verify and enc.get("crc") is None:
+            raise ValueError("decode_batch: verify=True needs enc[\"crc\"] (encode_batch(..., checksum=True))")
         count = enc["count"]
         table = enc.get("table")
         if out_off is None:
@@ -799,10 +821,14 @@ class Codec:
         if out_off.numel() == count + 1:
             fn = "dc_huff_decode_batch" if table is None else "dc_huff_decode_batch_shared"
             check(fn, getattr(self.L, fn)(self.ctx, C.byref(b), *tab, _ptr(buf), _ptr(out_off), buf.numel()))
+            if verify:
+                self.crc32_verify_batch(buf, enc["crc"], enc["status"], offsets=out_off)
         else:
             end = out_off + (enc["offsets"][1:] - enc["offsets"][:-1])
             fn = "dc_huff_decode_batch_scatter" if table is None else "dc_huff_decode_batch_shared_scatter"
             check(fn, getattr(self.L, fn)(self.ctx, C.byref(b), *tab, _ptr(buf), _ptr(out_off), _ptr(end), buf.numel()))
+            if verify:
+                self.crc32_verify_batch(buf, enc["crc"], enc["status"], beg=out_off, end=end)
         return out, out_off
 
     def decode_batch_ranges(self, enc, seg, first, count, out=None, out_off=None):
@@ -817,7 +843,8 @@ class Codec:
         default). Asynchronous, one launch. Returns (out, out_off, status): status[r] (int32,
         device) is range r's outcome, batch_status() the lowest failing range's. A failing range
         writes nothing and never stops the others. Only the chunks a range touches are read and
-        verified."""
+        verified. There is no checksum here: enc["crc"] is the CRC-32 of whole segments, and a
+        part of a segment has none (decode_batch(verify=True) checks whole segments)."""
         (seg, first, count), out_off, out, buf = self._range_lists(
             "decode_batch_ranges", (("seg", seg), ("first", first), ("count", count)), out, out_off)
         nr = count.numel()
@@ -886,9 +913,77 @@ class Codec:
         """0, or the status of the lowest-numbered failing segment of the last batch call on this
         codec (encode_batch with or without max_bits, batch_lens_pack, decode_batch,
         decode_batch_ranges, nyb_compress_batch,
-        nyb_decompress_batch_into, small_compress_batch, small_decompress_batch_into),
+        nyb_decompress_batch_into, small_compress_batch, small_decompress_batch_into, crc32_batch,
+        crc32_verify_batch: after a verify, the carried-over decode failures included),
         synchronising."""
         return int(self.L.dc_huff_batch_status(self.ctx))
+
+    # ---- checksums: CRC-32 per buffer (dc_gpu.h "checksums") -----------------------------------
+    CRC_TILE = 1024       # DC_CRC_TILE: the bytes a wave takes at a time
+    CRC_PIECE = 131072    # DC_CRC_PIECE: dc_crc32's bytes per wave
+    E_CHECKSUM = -9       # DC_E_CHECKSUM
+
+    def _crc_in(self, x, name):
+        if x.dtype != torch.uint8 or not x.is_cuda or not x.is_contiguous():
+            raise ValueError(f"{name} input: a contiguous uint8 device tensor")
+        return x
+
+    def _crc_lists(self, name, offsets, beg, end):
+        """(beg, end, count, keep): the two u64 device arrays of a buffer list, given as one
+        offsets array of count + 1 entries (passed as off and off + 1) or as two of count."""
+        if (offsets is None) == (beg is None and end is None) or (beg is None) != (end is None):
+            raise ValueError(f"{name}: either offsets (count + 1 entries) or beg and end (count entries each)")
+        if offsets is not None:
+            off = self._i64(offsets, range(1, 1 << 62), f"{name} offsets")
+            return off.data_ptr(), off.data_ptr() + 8, off.numel() - 1, (off,)
+        beg = self._i64(beg, range(0, 1 << 62), f"{name} beg")
+        end = self._i64(end, (beg.numel(),), f"{name} end")
+        return beg.data_ptr(), end.data_ptr(), beg.numel(), (beg, end)
+
+    def crc32(self, x):
+        """dc_crc32: the CRC-32 (zlib's) of the device uint8 tensor x, any size and alignment,
+        spread over the whole device. Returns a one-element uint32 device tensor. Asynchronous,
+        no host read, two launches."""
+        x = self._crc_in(x, "crc32")
+        out = self._t(1, torch.uint32)
+        check("dc_crc32", self.L.dc_crc32(self.ctx, _ptr(x), x.numel(), _ptr(out)))
+        return out
+
+    def crc32_batch(self, x, offsets=None, beg=None, end=None):
+        """dc_crc32_batch: the CRC-32 of every buffer x[beg[i]:end[i]] (int64 device tensors or
+        sequences of count entries each; any order, overlaps and gaps) or x[offsets[i]:
+        offsets[i+1]] (count + 1 entries). Returns device tensors (crc, status): uint32 and
+        int32, count entries each; a buffer with end < beg (DC_E_ARG) or end > x.numel()
+        (DC_E_CAPACITY) is not read and has crc 0; batch_status() gives the lowest failing
+        buffer's status. Asynchronous, one launch, no host read."""
+        x = self._crc_in(x, "crc32_batch")
+        pb, pe, count, keep = self._crc_lists("crc32_batch", offsets, beg, end)
+        crc = self._t(max(count, 1), torch.uint32)[:count]
+        status = self._t(max(count, 1), torch.int32)[:count]
+        check("dc_crc32_batch", self.L.dc_crc32_batch(self.ctx, _ptr(x), x.numel(), pb, pe, count, _ptr(crc), _ptr(status)))
+        return crc, status
+
+    def crc32_verify_batch(self, x, expect, status=None, offsets=None, beg=None, end=None):
+        """dc_crc32_verify_batch: the buffers of x (listed as in crc32_batch) against expect (a
+        uint32 device tensor of count entries, e.g. what crc32_batch gave for the inputs before
+        they were encoded). status (int32 device tensor, count entries) is in-out, so the
+        status a decode call returned can be handed straight on: an entry that is nonzero keeps
+        its value and its buffer is not read; an entry that is 0 becomes DC_E_ARG /
+        DC_E_CAPACITY for a bad range and DC_E_CHECKSUM (-9) when the buffer's CRC-32 is not
+        expect[i]. A fresh zero array is used when none is given. Returns status;
+        batch_status() then answers for the decode and the verify together. Asynchronous, one
+        launch, no host read."""
+        x = self._crc_in(x, "crc32_verify_batch")
+        pb, pe, count, keep = self._crc_lists("crc32_verify_batch", offsets, beg, end)
+        if expect.dtype != torch.uint32 or not expect.is_cuda or not expect.is_contiguous() or expect.numel() != count:
+            raise ValueError(f"crc32_verify_batch expect: a contiguous uint32 device tensor of {count} entries")
+        if status is None:
+            status = torch.zeros(count, dtype=torch.int32, device=x.device)
+        elif status.dtype != torch.int32 or not status.is_cuda or not status.is_contiguous() or status.numel() != count:
+            raise ValueError(f"crc32_verify_batch status: a contiguous int32 device tensor of {count} entries")
+        check("dc_crc32_verify_batch", self.L.dc_crc32_verify_batch(self.ctx, _ptr(x), x.numel(), pb, pe, count,
+                                                                    _ptr(expect), _ptr(status)))
+        return status
 
     # ---- C5 fused front-end encode (small_compression.c front-end, then Huffman; one pass) -----
     def small_huff_plan(self, x, n_ary: int = 16, max_symbol_value: int = 258, hist=None, table=None, total=None):

@@ -34,7 +34,8 @@ enum {
     DC_E_STATE = -5,         /* stage called out of order (e.g. pack before hist of that input) */
     DC_E_CAPACITY = -6,      /* output buffer too small */
     DC_E_STREAM = -7,        /* corrupt compressed stream */
-    DC_E_FALLBACK = -8       /* the fused C5 path does not apply to this input: run the two stages */
+    DC_E_FALLBACK = -8,      /* the fused C5 path does not apply to this input: run the two stages */
+    DC_E_CHECKSUM = -9       /* a decoded buffer's CRC-32 is not the one stored for it ("checksums") */
 };
 
 #define DC_BLOCK_BYTES 32768u   /* encoder block: one histogram + one bit offset each */
@@ -541,7 +542,8 @@ int dc_huff_batch_status(dc_ctx *ctx);
  * then mode, bits, the payload and the u16 index per segment.
  * Decoding under a different table is reported as DC_E_STREAM whenever a chunk then fails to
  * decode to exactly its symbols in exactly its bits; as in batch v1 there is no checksum, so a
- * wrong table that happens to satisfy every chunk is not detected. A window that decodes to a
+ * wrong table that happens to satisfy every chunk is not detected ("checksums" below: the CRC-32
+ * per segment a caller can keep beside the batch and verify after the decode). A window that decodes to a
  * symbol >= 256 (the table's canonical arrays hold up to DC_MAX_SYMS symbols) is a corrupt stream,
  * never a byte written.
  * Host argument rules are batch v1's without the d_lens test, and d_table must not be NULL. All
@@ -842,6 +844,64 @@ int dc_small_compress_body_write(dc_ctx *ctx, const uint8_t *d_in, uint64_t len,
                                  uint8_t *d_out, uint64_t *h_len);
 /* decode of a body (every byte: >= 0x80 -> ' ' + byte - 0x80); d_out capacity >= 2*m */
 int dc_small_decompress_body(dc_ctx *ctx, const uint8_t *d_in, uint64_t m, uint8_t *d_out, uint64_t *h_out_len);
+
+/* ---- checksums: CRC-32 per buffer on the device, verified after decode ------------------------
+ * No batch format here carries a checksum, and no decoder can tell a damaged stored segment, a
+ * code swapped for another of its length, a damaged literal byte or a wrong shared table from the
+ * real thing. These calls give the caller one more per-buffer array to keep beside mode / bits /
+ * the offsets: the CRC-32 of every buffer before it is encoded, checked against the decoded
+ * bytes. They change no format and no other call.
+ *
+ * The algorithm is CRC-32 as zlib, PNG and gzip compute it (reflected polynomial 0xEDB88320, the
+ * register started at all ones and inverted at the end), so any host tool can check a stored
+ * value. The arithmetic is csrc/dc_crc32.h.
+ *
+ * dc_crc32_host: the host's running form, as zlib's crc32(): start from crc = 0 and hand each
+ * result to the next piece. dc_crc32_combine: crc(A || B) from crc(A), crc(B) and |B|, any |B|.
+ * Both are pure host arithmetic.
+ *
+ * dc_crc32_batch: buffer i = d_in[d_beg[i] .. d_end[i]), two device u64 arrays of count entries
+ * that the kernel reads; for the usual offsets array of count + 1 entries pass off and off + 1
+ * (the two may alias this way). Buffers may have any byte alignment, any length (0 included: its
+ * CRC is 0; there is no maximum), any order, overlaps and gaps (the scatter layouts of
+ * dc_huff_decode_batch_scatter). d_crc[i] receives the buffer's CRC-32, d_status[i]
+ *   DC_E_ARG       d_end[i] < d_beg[i]
+ *   DC_E_CAPACITY  d_end[i] > in_cap
+ *   DC_OK          otherwise;
+ * in the two failing cases nothing of the buffer is read and d_crc[i] is 0. A bad buffer never
+ * stops the others, and nothing past entry count - 1 of either output is written. (Loads are whole
+ * aligned 16-B granules: up to 15 bytes beside a buffer, inside d_in's allocation, are read and
+ * masked.)
+ *
+ * dc_crc32_verify_batch: d_status is in-out, so the status array a decode call just wrote can be
+ * handed straight on. An entry that is nonzero on entry is skipped: its buffer is not read (a
+ * failed nybble stream's range is unspecified) and its status stays. An entry that is DC_OK on
+ * entry gets the two tests above and then becomes DC_E_CHECKSUM when the buffer's CRC is not
+ * d_expect[i].
+ *
+ * Both batch calls: asynchronous on the context's stream, no host read, ONE launch whatever the
+ * count (a wave per buffer in tiles of DC_CRC_TILE bytes, on a persistent grid that
+ * DC_OPT_BATCH_GRID sizes); count 0 returns DC_OK without a launch; DC_E_ARG for a NULL context,
+ * a NULL pointer with count > 0, or count > DC_RANGES_MAX. The context's first-failure slot
+ * (dc_huff_batch_status) gets the lowest index whose status is nonzero after the call, for verify
+ * the carried-over entries included: one dc_huff_batch_status after decode plus verify answers
+ * for both. A buffer is never split between waves: long buffers in a batch are correct, and
+ * dc_crc32 is the call for one huge buffer.
+ *
+ * dc_crc32: one buffer of any size and alignment spread over the whole device, e.g. a 1 GiB
+ * stream, a DCH1 blob or a whole payload array: a wave per piece of DC_CRC_PIECE bytes writes the
+ * piece's CRC times x^(8 * the bytes after the piece) into context scratch (4 B per piece), and a
+ * one-workgroup launch xors them into *d_crc (device). Two launches, asynchronous, no host read;
+ * n = 0 writes 0 without a launch. */
+#define DC_CRC_TILE 1024u        /* bytes a wave takes at a time: 64 lanes x 16 B */
+#define DC_CRC_PIECE 131072u     /* dc_crc32: bytes per wave */
+uint32_t dc_crc32_host(uint32_t crc, const void *data, size_t n);
+uint32_t dc_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b);
+int dc_crc32(dc_ctx *ctx, const uint8_t *d_in, uint64_t n, uint32_t *d_crc);
+int dc_crc32_batch(dc_ctx *ctx, const uint8_t *d_in, uint64_t in_cap, const uint64_t *d_beg, const uint64_t *d_end,
+                   uint64_t count, uint32_t *d_crc, int32_t *d_status);
+int dc_crc32_verify_batch(dc_ctx *ctx, const uint8_t *d_in, uint64_t in_cap, const uint64_t *d_beg,
+                          const uint64_t *d_end, uint64_t count, const uint32_t *d_expect, int32_t *d_status);
 
 #ifdef __cplusplus
 }
