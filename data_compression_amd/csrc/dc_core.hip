@@ -6277,55 +6277,68 @@ __global__ __launch_bounds__(256) void k_copy_probe(const uint4 *__restrict__ sr
 // =====================================================================================
 #define DC_MAX_EVENTS 1024   /* HIP-event pairs per timing window (a C5 step launches ~40 kernels) */
 
+// A growable device buffer of the context's workspace (ensure): the pointer and its capacity in
+// bytes, read as a T *. Every one is a member of dc_ctx::ws, which ctx_free walks.
+struct DevBuf { void *p; size_t cap; };
+template <class T> struct Buf : DevBuf {
+    T *get() const { return static_cast<T *>(p); }
+    operator T *() const { return get(); }
+};
+
 struct dc_ctx {
     int device;
     hipStream_t stream;
     bool own_stream;
-    // workspace
-    uint16_t *d_bh;         size_t bh_cap;        // block histograms (u16 x 256 per block)
-    uint64_t *d_off;        size_t off_cap;       // nblocks + 1
-    uint32_t *d_plan;       size_t plan_cap;      // plan: per-block local offsets + workgroup totals
-    uint64_t *d_msym;       size_t msym_cap;      // C5 fused front-end: first symbol index per block (+ total)
-    uint32_t *d_gexp;       size_t gexp_cap;      // C5 decode: symbols >= 0x80 per group (dc_small_huff_decode)
+    // the growable workspace: a buffer is one declaration here and its uses (ctx_free frees them all)
+    struct Workspace {
+        Buf<uint16_t> bh;        // block histograms (u16 x 256 per block)
+        Buf<uint64_t> off;       // nblocks + 1
+        Buf<uint32_t> plan;      // plan: per-block local offsets + workgroup totals
+        Buf<uint64_t> msym;      // C5 fused front-end: first symbol index per block (+ total)
+        Buf<uint32_t> gexp;      // C5 decode: symbols >= 0x80 per group (dc_small_huff_decode)
+        Buf<uint64_t> fix;       // decode redo: a u64 chunk mask per group
+        Buf<uint64_t> fixpos;    // decode redo: bit offset of a flagged chunk
+        Buf<uint64_t> rng;       // range decode: items per range, then their offsets (+ total)
+        Buf<uint64_t> hb;        // batch codec: first failure, then payload bytes and chunks per segment
+        Buf<uint32_t> crcp;      // checksums: dc_crc32's weighted piece CRCs
+        Buf<uint8_t> scr;        // per-wave garbage sinks of the decoders
+        Buf<uint4> summ;         // transducers: tile summaries, then the groups' (fsm_count)
+        Buf<uint64_t> entry;     // transducers: entry state and offset per group of tiles
+        Buf<MtfSum> mtf;         // adaptive nybble: tile summaries + entries, all levels
+        Buf<uint8_t> rk;         // adaptive nybble: rank per element
+        Buf<uint4> mrec;         // adaptive nybble: step records, MTF_REC per tile
+        Buf<uint2> mhead;        // adaptive nybble: records per tile
+        Buf<uint4> fraw;         // adaptive nybble: the encoder's tile summaries (k_mtf_resolve)
+        Buf<uint32_t> actl;      // adaptive nybble decode: control words of a segment
+        Buf<uint8_t> kscr;       // chunked nybble: per-chunk streams before packing
+        Buf<uint64_t> klens;     // chunked nybble: stream length per chunk
+    } ws;
+    // fixed allocations (made by ctx_init but for the two lazy ones; ctx_free frees them)
     int *d_err;                                   // [8] text parse
     // error flags of plan/pack and of decode in rotating slots (32 x 4 ints each): every call
     // takes the next slot, which a kernel of the call before cleared (no memset launch)
-    int *d_errp, *d_errd;
+    int *d_errp, *d_errd;                         // (one allocation: d_errd = d_errp + 128)
+    uint32_t *d_queue;                            // decode tuple scheduler heads (D8Sched)
+    uint32_t *d_crct;                             // checksums: the lookup tables (CRC_T_WORDS, written once at create)
+    uint64_t *d_hloc;                             // this context's last histogram (256 u64; hist[] may be all-reduced)
+    uint32_t *d_hflag;                            // histogram accumulator (256 u64) + done counter, zero between launches
+    uint64_t *d_meta;                             // small device scalars
+    uint32_t *d_astate;                           // adaptive nybble decode: lists + byte between segments (lazy: adec_fast)
+    uint64_t *h_pinned;                           // pinned host block of read_back / upload (PINNED_WORDS)
+    MtfSum *h_mtf;                                // adaptive nybble: pinned entry lists (lazy: mtf_run)
+    // state between calls
     uint32_t gen_p, gen_d;
     const dc_dtable *dec_fresh;                   // decoder tables current: this context's last pack built them,
     uint64_t dec_fresh_gen;                       // ... while g_table_gen had this value (see table_written)
-    uint32_t *d_queue;                            // decode tuple scheduler heads (D8Sched)
-    uint32_t *d_fix;        size_t fix_cap;       // decode redo: a u64 chunk mask per group
-    uint32_t *d_fixpos;     size_t fixpos_cap;    // decode redo: bit offset of a flagged chunk
     uint64_t last_groups;                         // groups of the last S = 64 decode (redo mask length)
-    uint64_t *d_rng;        size_t rng_cap;       // range decode: items per range, then their offsets (+ total)
-    uint64_t *d_hb;         size_t hb_cap;        // batch codec: first failure, then payload bytes and chunks per segment
-    uint32_t *d_crct;                             // checksums: the lookup tables (CRC_T_WORDS, written once at create)
-    uint32_t *d_crcp;       size_t crcp_cap;      // checksums: dc_crc32's weighted piece CRCs
-    uint64_t *d_hloc;                             // this context's last histogram (256 u64; hist[] may be all-reduced)
     const dc_dtable *plan_table;                  // the table and device total of the last plan
     uint64_t *plan_total;
-    void *d_scr;            size_t scr_cap;       // per-wave garbage sinks of the decoders
-    uint64_t *d_meta;                             // small device scalars
-    uint4 *d_summ;          size_t summ_cap;
-    uint64_t *d_entry;      size_t entry_cap;
-    MtfSum *d_mtf;          size_t mtf_cap;       // adaptive nybble: tile summaries + entries, all levels
-    uint8_t *d_rk;          size_t rk_cap;        // adaptive nybble: rank per element
-    uint4 *d_mrec;          size_t mrec_cap;      // adaptive nybble: step records, MTF_REC per tile
-    uint2 *d_mhead;         size_t mhead_cap;     // adaptive nybble: records per tile
-    uint4 *d_fraw;          size_t fraw_cap;      // adaptive nybble: the encoder's tile summaries (k_mtf_resolve)
-    bool summ_fresh;                              // d_summ holds them too (no scan since)
-    MtfSum *h_mtf;                                // adaptive nybble: pinned entry lists (mtf_run)
-    uint32_t *d_actl;       size_t actl_cap;      // adaptive nybble decode: control words of a segment
-    uint32_t *d_astate;                           // adaptive nybble decode: lists + byte between segments
-    const uint8_t *rk_in; uint64_t rk_len;        // identity of the input the ranks belong to
-    const uint8_t *fsm_in; uint64_t fsm_len, fsm_nelem; int fsm_mode;   // input of the last transducer plan
-    uint8_t *d_kscr;        size_t kscr_cap;      // chunked nybble: per-chunk streams before packing
-    uint64_t *d_klens;      size_t klens_cap;     // chunked nybble: stream length per chunk
-    uint64_t *h_pinned;                           // pinned host scalars
+    bool plan_ok;
     const uint8_t *hist_in; uint64_t hist_n;      // identity of the last dc_huff_hist input
     bool hist_fe;                                 // ... histogram of its C5 front-end output (dc_small_huff_plan)
-    bool plan_ok;
+    bool summ_fresh;                              // ws.summ holds ws.fraw's summaries too (no scan since)
+    const uint8_t *rk_in; uint64_t rk_len;        // identity of the input the ranks belong to
+    const uint8_t *fsm_in; uint64_t fsm_len, fsm_nelem; int fsm_mode;   // input of the last transducer plan
     // tuning options (dc_ctx_set_option; initial values from the environment, read once here)
     uint32_t opt_hist_grid;       // histogram workgroups (0: default 512)
     uint32_t opt_pack_grid;       // pack: workgroups of k_huff_pack (0: a block pair each; A/B builds: blocks per wave of k_huff_pack_w)
@@ -6335,17 +6348,18 @@ struct dc_ctx {
     uint32_t opt_d8_static;       // decoder: static share of the tuples, percent (0..100)
     uint32_t opt_decode_general;  // 1: always the general decoder (k_huff_decode)
     uint32_t opt_hist_pf;         // histogram: blocks of loads in flight ahead (1..2, 0 = default 2)
-    uint32_t *d_hflag;            // histogram accumulator (256 u64) + done counter, zero between launches
     uint32_t opt_decode_variant;  // fast decoder: 0 one code per lookup (k_huff_decode8), 1 up to 3 (k_huff_decode9)
     uint32_t opt_adec_v1;         // adaptive nybble decode: 0 control words + k_nyb_resolve_c, 1 = the one-pass
                                   // k_nyb_adec, 2 = r2's k_nyb_resolve, 3 = k_nyb_resolve_s (A/B)
     // timing
-    int timing;
-    int nev;
+    int timing, nev;
     hipEvent_t ev0[DC_MAX_EVENTS], ev1[DC_MAX_EVENTS];
     const char *evname[DC_MAX_EVENTS];
     bool events_made;
 };
+static_assert(sizeof(dc_ctx::Workspace) % sizeof(DevBuf) == 0 && sizeof(Buf<uint4>) == sizeof(DevBuf),
+              "dc_ctx::ws is DevBufs and nothing else");
+#define PINNED_WORDS 16
 
 #define HIPCHK(x) do { if ((x) != hipSuccess) return DC_E_HIP; } while (0)
 
@@ -6371,25 +6385,57 @@ static bool dec_tables_fresh(const dc_ctx *c, const dc_dtable *t)
     return c->dec_fresh == t && c->dec_fresh_gen == g_table_gen.load(std::memory_order_relaxed);
 }
 
-static int ensure(void **p, size_t *cap, size_t bytes)
+// b holds at least `bytes` (4096 at the least) after this; growing frees first and keeps nothing
+static int ensure(DevBuf &b, size_t bytes)
 {
-    if (*cap >= bytes && *p) return DC_OK;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
+    if (b.cap >= bytes && b.p) return DC_OK;
+    if (b.p) (void)hipFree(b.p);
+    b.p = nullptr; b.cap = 0;
     size_t want = bytes < 4096 ? 4096 : bytes;
-    if (hipMalloc(p, want) != hipSuccess) { *p = nullptr; return DC_E_HIP; }
-    *cap = want;
+    if (hipMalloc(&b.p, want) != hipSuccess) { b.p = nullptr; return DC_E_HIP; }
+    b.cap = want;
     return DC_OK;
 }
 
-static void t_begin(dc_ctx *c, const char *name, int *slot)
+// Device -> host through the pinned block: n values of T from d_src into h_dst, one copy and one
+// wait. The values are the caller's from then on: no call reads what another left in the block.
+template <class T> static int read_back(dc_ctx *c, const void *d_src, T *h_dst, size_t n = 1)
 {
-    *slot = -1;
-    if (!c->timing || c->nev >= DC_MAX_EVENTS) return;
-    *slot = c->nev++;
-    c->evname[*slot] = name;
-    (void)hipEventRecord(c->ev0[*slot], c->stream);
+    static_assert(std::is_trivially_copyable<T>::value, "plain values");
+    if (n * sizeof(T) > PINNED_WORDS * sizeof(uint64_t)) return DC_E_ARG;
+    HIPCHK(hipMemcpyAsync(c->h_pinned, d_src, n * sizeof(T), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    memcpy(h_dst, c->h_pinned, n * sizeof(T));
+    return DC_OK;
+}
+// ... and two values from two places: two copies, one wait
+template <class A, class B> static int read_back2(dc_ctx *c, const void *d_a, A *h_a, const void *d_b, B *h_b)
+{
+    static_assert(sizeof(A) <= 8 && sizeof(B) <= 8, "a word of the block each");
+    HIPCHK(hipMemcpyAsync(c->h_pinned, d_a, sizeof(A), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(c->h_pinned + 1, d_b, sizeof(B), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    memcpy(h_a, c->h_pinned, sizeof(A));
+    memcpy(h_b, c->h_pinned + 1, sizeof(B));
+    return DC_OK;
+}
+// Host -> device through the pinned block, no wait: the bytes stay at word `word` of the block until the
+// copy runs, so uploads before one wait take words of their own (a later read_back is ordered behind them).
+static int upload(dc_ctx *c, void *d_dst, const void *h_src, size_t bytes, size_t word = 0)
+{
+    if (word * sizeof(uint64_t) + bytes > PINNED_WORDS * sizeof(uint64_t)) return DC_E_ARG;
+    memcpy(c->h_pinned + word, h_src, bytes);
+    HIPCHK(hipMemcpyAsync(d_dst, c->h_pinned + word, bytes, hipMemcpyHostToDevice, c->stream));
+    return DC_OK;
+}
+
+static int t_begin(dc_ctx *c, const char *name)
+{
+    if (!c->timing || c->nev >= DC_MAX_EVENTS) return -1;
+    const int slot = c->nev++;
+    c->evname[slot] = name;
+    (void)hipEventRecord(c->ev0[slot], c->stream);
+    return slot;
 }
 static void t_end(dc_ctx *c, int slot)
 {
@@ -6397,7 +6443,7 @@ static void t_end(dc_ctx *c, int slot)
 }
 
 #define LAUNCH(ctx, name, kern, grid, block, ...) do {                         \
-        int _slot; t_begin(ctx, name, &_slot);                                  \
+        const int _slot = t_begin(ctx, name);                                   \
         hipLaunchKernelGGL(kern, dim3(grid), dim3(block), 0, ctx->stream, __VA_ARGS__); \
         if (hipGetLastError() != hipSuccess) return DC_E_HIP;                   \
         t_end(ctx, _slot);                                                      \
@@ -6421,10 +6467,70 @@ extern "C" {
 const char *dc_version(void) { return DC_VERSION; }
 size_t dc_dtable_size(void) { return sizeof(dc_dtable); }
 
-static int ctx_create(dc_ctx **out, int device, void *stream, bool own);
+// the static dictionary (NYB_DICT, its one definition): the byte of rank k, the rank of a byte (0xFF: absent)
+static uint8_t dict_byte(int k) { return (uint8_t)(NYB_DICT >> (8 * k)); }
+static uint8_t dict_rank(uint8_t b)
+{
+    for (int k = 0; k < 8; ++k) if (dict_byte(k) == b) return (uint8_t)k;
+    return 0xFF;
+}
 
-int dc_ctx_create(dc_ctx **out, int device, void *stream) { return ctx_create(out, device, stream, false); }
-int dc_ctx_create_owned(dc_ctx **out, int device) { return ctx_create(out, device, nullptr, true); }
+// Everything a context owns, whatever of it exists: ctx_create's failure paths and dc_ctx_destroy
+static void ctx_free(dc_ctx *c)
+{
+    DevBuf *const ws = reinterpret_cast<DevBuf *>(&c->ws);
+    for (size_t i = 0; i < sizeof(c->ws) / sizeof(DevBuf); ++i)
+        if (ws[i].p) (void)hipFree(ws[i].p);
+    void *const fixed[] = {c->d_err, c->d_errp, c->d_queue, c->d_crct, c->d_hloc, c->d_hflag, c->d_meta, c->d_astate};
+    for (void *p : fixed)
+        if (p) (void)hipFree(p);
+    if (c->h_pinned) (void)hipHostFree(c->h_pinned);
+    if (c->h_mtf) (void)hipHostFree(c->h_mtf);
+    if (c->events_made)
+        for (int i = 0; i < DC_MAX_EVENTS; ++i) { (void)hipEventDestroy(c->ev0[i]); (void)hipEventDestroy(c->ev1[i]); }
+    if (c->own_stream) (void)hipStreamDestroy(c->stream);
+    free(c);
+}
+
+// the stream and the fixed allocations of a zeroed context (on an error the caller frees what was made)
+static int ctx_init(dc_ctx *c, void *stream, bool own)
+{
+    if (!own) c->stream = (hipStream_t)stream;   // NULL = default stream
+    else {
+        HIPCHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+        c->own_stream = true;
+    }
+    HIPCHK(hipMalloc((void **)&c->d_err, 16 * sizeof(int)));
+    HIPCHK(hipMalloc((void **)&c->d_errp, 2 * 128 * sizeof(int)));
+    HIPCHK(hipMemset(c->d_errp, 0, 2 * 128 * sizeof(int)));
+    c->d_errd = c->d_errp + 128;
+    HIPCHK(hipMalloc((void **)&c->d_meta, 16 * sizeof(uint64_t)));
+    HIPCHK(hipHostMalloc((void **)&c->h_pinned, PINNED_WORDS * sizeof(uint64_t), 0));
+    HIPCHK(hipMalloc((void **)&c->d_hflag, 4096));
+    HIPCHK(hipMemset(c->d_hflag, 0, 4096));
+    HIPCHK(hipMalloc((void **)&c->d_hloc, 256 * sizeof(uint64_t)));
+    HIPCHK(hipMemset(c->d_hloc, 0, 256 * sizeof(uint64_t)));
+    HIPCHK(hipMalloc((void **)&c->d_queue, D8_QWORDS * sizeof(uint32_t)));
+    HIPCHK(hipMemset(c->d_queue, 0, D8_QWORDS * sizeof(uint32_t)));
+    HIPCHK(hipMalloc((void **)&c->d_crct, CRC_T_WORDS * sizeof(uint32_t)));
+    HIPCHK(hipMemcpy(c->d_crct, crc_host_tables(), CRC_T_WORDS * sizeof(uint32_t), hipMemcpyHostToDevice));
+    c->opt_d8_static = D8_STATIC_PCT;
+    {   // A/B knobs (environment; tools/kern_ab.py sets the same options per context), read once and clamped
+        const char *e;
+        if ((e = getenv("DC_HIST_GRID"))) (void)dc_ctx_set_option(c, DC_OPT_HIST_GRID, atoll(e));
+        if ((e = getenv("DC_PACK_GRID"))) (void)dc_ctx_set_option(c, DC_OPT_PACK_GRID, atoll(e));
+        if ((e = getenv("DC_D8_STATIC"))) (void)dc_ctx_set_option(c, DC_OPT_DECODE_STATIC_PCT, atoll(e));
+        if ((e = getenv("DC_DECODE_V7"))) (void)dc_ctx_set_option(c, DC_OPT_DECODE_GENERAL, atoll(e) != 0);
+    }
+    if (g_rank_uploaded != c->device) {
+        uint8_t rank[256];
+        memset(rank, 0xFF, sizeof(rank));
+        for (int r = 0; r < 8; ++r) rank[dict_byte(r)] = (uint8_t)r;
+        HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(c_static_rank), rank, 256));
+        g_rank_uploaded = c->device;
+    }
+    return DC_OK;
+}
 
 static int ctx_create(dc_ctx **out, int device, void *stream, bool own)
 {
@@ -6436,157 +6542,47 @@ static int ctx_create(dc_ctx **out, int device, void *stream, bool own)
     dc_ctx *c = (dc_ctx *)calloc(1, sizeof(dc_ctx));
     if (!c) return DC_E_ARG;
     c->device = device;
-    if (!own) { c->stream = (hipStream_t)stream; c->own_stream = false; }   // NULL = default stream
-    else {
-        if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { free(c); return DC_E_HIP; }
-        c->own_stream = true;
-    }
-    if (hipMalloc((void **)&c->d_err, 16 * sizeof(int)) != hipSuccess ||
-        hipMalloc((void **)&c->d_errp, 2 * 128 * sizeof(int)) != hipSuccess ||
-        hipMemset(c->d_errp, 0, 2 * 128 * sizeof(int)) != hipSuccess ||
-        hipMalloc((void **)&c->d_meta, 16 * sizeof(uint64_t)) != hipSuccess ||
-        hipHostMalloc((void **)&c->h_pinned, 16 * sizeof(uint64_t), 0) != hipSuccess) {
-        free(c);
-        return DC_E_HIP;
-    }
-    c->d_errd = c->d_errp + 128;
-    if (hipMalloc((void **)&c->d_hflag, 4096) != hipSuccess || hipMemset(c->d_hflag, 0, 4096) != hipSuccess ||
-        hipMalloc((void **)&c->d_hloc, 256 * sizeof(uint64_t)) != hipSuccess ||
-        hipMemset(c->d_hloc, 0, 256 * sizeof(uint64_t)) != hipSuccess) {
-        free(c);
-        return DC_E_HIP;
-    }
-    if (hipMalloc((void **)&c->d_queue, D8_QWORDS * sizeof(uint32_t)) != hipSuccess ||
-        hipMemset(c->d_queue, 0, D8_QWORDS * sizeof(uint32_t)) != hipSuccess) {
-        free(c);
-        return DC_E_HIP;
-    }
-    if (hipMalloc((void **)&c->d_crct, CRC_T_WORDS * sizeof(uint32_t)) != hipSuccess ||
-        hipMemcpy(c->d_crct, crc_host_tables(), CRC_T_WORDS * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) {
-        free(c);
-        return DC_E_HIP;
-    }
-    c->opt_d8_static = D8_STATIC_PCT;
-    {   // A/B knobs (environment; tools/kern_ab.py sets the same options per context), read once and clamped
-        const char *e;
-        if ((e = getenv("DC_HIST_GRID"))) (void)dc_ctx_set_option(c, DC_OPT_HIST_GRID, atoll(e));
-        if ((e = getenv("DC_PACK_GRID"))) (void)dc_ctx_set_option(c, DC_OPT_PACK_GRID, atoll(e));
-        if ((e = getenv("DC_D8_STATIC"))) (void)dc_ctx_set_option(c, DC_OPT_DECODE_STATIC_PCT, atoll(e));
-        if ((e = getenv("DC_DECODE_V7"))) (void)dc_ctx_set_option(c, DC_OPT_DECODE_GENERAL, atoll(e) != 0);
-    }
-    if (g_rank_uploaded != device) {
-        uint8_t rank[256];
-        memset(rank, 0xFF, sizeof(rank));
-        const char *t = " etaoins";
-        for (int r = 0; r < 8; ++r) rank[(uint8_t)t[r]] = (uint8_t)r;
-        if (hipMemcpyToSymbol(HIP_SYMBOL(c_static_rank), rank, 256) != hipSuccess) { free(c); return DC_E_HIP; }
-        g_rank_uploaded = device;
-    }
+    if (const int r = ctx_init(c, stream, own)) { ctx_free(c); return r; }
     *out = c;
     return DC_OK;
 }
+int dc_ctx_create(dc_ctx **out, int device, void *stream) { return ctx_create(out, device, stream, false); }
+int dc_ctx_create_owned(dc_ctx **out, int device) { return ctx_create(out, device, nullptr, true); }
 
 void dc_ctx_destroy(dc_ctx *c)
 {
     if (!c) return;
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
-    if (c->d_bh) (void)hipFree(c->d_bh);
-    if (c->d_off) (void)hipFree(c->d_off);
-    if (c->d_plan) (void)hipFree(c->d_plan);
-    if (c->d_msym) (void)hipFree(c->d_msym);
-    if (c->d_gexp) (void)hipFree(c->d_gexp);
-    if (c->d_err) (void)hipFree(c->d_err);
-    if (c->d_errp) (void)hipFree(c->d_errp);
-    if (c->d_hflag) (void)hipFree(c->d_hflag);
-    if (c->d_hloc) (void)hipFree(c->d_hloc);
-    if (c->d_queue) (void)hipFree(c->d_queue);
-    if (c->d_fix) (void)hipFree(c->d_fix);
-    if (c->d_fixpos) (void)hipFree(c->d_fixpos);
-    if (c->d_rng) (void)hipFree(c->d_rng);
-    if (c->d_hb) (void)hipFree(c->d_hb);
-    if (c->d_crct) (void)hipFree(c->d_crct);
-    if (c->d_crcp) (void)hipFree(c->d_crcp);
-    if (c->d_scr) (void)hipFree(c->d_scr);
-    if (c->d_meta) (void)hipFree(c->d_meta);
-    if (c->d_summ) (void)hipFree(c->d_summ);
-    if (c->d_entry) (void)hipFree(c->d_entry);
-    if (c->d_mtf) (void)hipFree(c->d_mtf);
-    if (c->d_rk) (void)hipFree(c->d_rk);
-    if (c->d_mrec) (void)hipFree(c->d_mrec);
-    if (c->d_mhead) (void)hipFree(c->d_mhead);
-    if (c->d_fraw) (void)hipFree(c->d_fraw);
-    if (c->h_mtf) (void)hipHostFree(c->h_mtf);
-    if (c->d_actl) (void)hipFree(c->d_actl);
-    if (c->d_astate) (void)hipFree(c->d_astate);
-    if (c->d_kscr) (void)hipFree(c->d_kscr);
-    if (c->d_klens) (void)hipFree(c->d_klens);
-    if (c->h_pinned) (void)hipHostFree(c->h_pinned);
-    if (c->events_made)
-        for (int i = 0; i < DC_MAX_EVENTS; ++i) { (void)hipEventDestroy(c->ev0[i]); (void)hipEventDestroy(c->ev1[i]); }
-    if (c->own_stream) (void)hipStreamDestroy(c->stream);
-    free(c);
+    ctx_free(c);
 }
 
 int dc_ctx_set_option(dc_ctx *c, int option, int64_t value)
 {
     if (!c) return DC_E_ARG;
-    switch (option) {
-    case DC_OPT_HIST_GRID:   // 0 = default; the kernel's per-workgroup bin totals are u64
-        if (value < 0 || value > (1 << 20)) return DC_E_ARG;
-        c->opt_hist_grid = (uint32_t)value;
-        return DC_OK;
-    case DC_OPT_PACK_GRID:
-        if (value < 0 || value > (1 << 24)) return DC_E_ARG;
-        c->opt_pack_grid = (uint32_t)value;
-        return DC_OK;
-    case DC_OPT_DECODE_STATIC_PCT:
-        if (value < 0 || value > 100) return DC_E_ARG;
-        c->opt_d8_static = (uint32_t)value;
-        return DC_OK;
-    case DC_OPT_DECODE_GENERAL:
-        if (value != 0 && value != 1) return DC_E_ARG;
-        c->opt_decode_general = (uint32_t)value;
-        return DC_OK;
-    case DC_OPT_DECODE_VARIANT:   // 1: k_huff_decode9, in DC_AB_KERNELS builds only
-#ifdef DC_AB_KERNELS
-        if (value < 0 || value > 1) return DC_E_ARG;
-#else
-        if (value != 0) return DC_E_ARG;
+    // an option's field and largest value; ab: any value but 0 in DC_AB_KERNELS builds only
+    static const struct { int id; uint32_t dc_ctx::*field; int64_t max; bool ab; } opts[] = {
+        {DC_OPT_HIST_GRID, &dc_ctx::opt_hist_grid, 1 << 20, false},   // 0 = default; the kernel's per-workgroup bin totals are u64
+        {DC_OPT_PACK_GRID, &dc_ctx::opt_pack_grid, 1 << 24, false},
+        {DC_OPT_DECODE_STATIC_PCT, &dc_ctx::opt_d8_static, 100, false},
+        {DC_OPT_DECODE_GENERAL, &dc_ctx::opt_decode_general, 1, false},
+        {DC_OPT_DECODE_VARIANT, &dc_ctx::opt_decode_variant, 1, true},   // 1: k_huff_decode9
+        {DC_OPT_NYB_ADEC_V1, &dc_ctx::opt_adec_v1, 3, true},             // 1-3: the A/B resolves
+        {DC_OPT_HIST_PREFETCH, &dc_ctx::opt_hist_pf, 3, false},
+        {DC_OPT_PACK_BLOCK, &dc_ctx::opt_pack_block, 7, true},           // 2/3: k_huff_pack_w
+        {DC_OPT_NYB_WTILE_OFF, &dc_ctx::opt_nyb_wtile_off, 1, false},
+        {DC_OPT_BATCH_GRID, &dc_ctx::opt_batch_grid, 65536, false},
+    };
+    for (const auto &o : opts) {
+        if (o.id != option) continue;
+#ifndef DC_AB_KERNELS
+        if (o.ab && value != 0) return DC_E_ARG;
 #endif
-        c->opt_decode_variant = (uint32_t)value;
+        if (value < 0 || value > o.max) return DC_E_ARG;
+        c->*o.field = (uint32_t)value;
         return DC_OK;
-    case DC_OPT_NYB_ADEC_V1:   // 1-3: the A/B resolves, in DC_AB_KERNELS builds only
-#ifdef DC_AB_KERNELS
-        if (value < 0 || value > 3) return DC_E_ARG;
-#else
-        if (value != 0) return DC_E_ARG;
-#endif
-        c->opt_adec_v1 = (uint32_t)value;
-        return DC_OK;
-    case DC_OPT_HIST_PREFETCH:
-        if (value < 0 || value > 3) return DC_E_ARG;
-        c->opt_hist_pf = (uint32_t)value;
-        return DC_OK;
-    case DC_OPT_PACK_BLOCK:   // 2/3: k_huff_pack_w, in DC_AB_KERNELS builds only
-#ifdef DC_AB_KERNELS
-        if (value < 0 || value > 7) return DC_E_ARG;
-#else
-        if (value != 0) return DC_E_ARG;
-#endif
-        c->opt_pack_block = (uint32_t)value;
-        return DC_OK;
-    case DC_OPT_NYB_WTILE_OFF:
-        if (value != 0 && value != 1) return DC_E_ARG;
-        c->opt_nyb_wtile_off = (uint32_t)value;
-        return DC_OK;
-    case DC_OPT_BATCH_GRID:
-        if (value < 0 || value > 65536) return DC_E_ARG;
-        c->opt_batch_grid = (uint32_t)value;
-        return DC_OK;
-    default:
-        return DC_E_ARG;
     }
+    return DC_E_ARG;
 }
 
 int dc_ctx_sync(dc_ctx *c) { return (c && hipStreamSynchronize(c->stream) == hipSuccess) ? DC_OK : DC_E_HIP; }
@@ -6664,14 +6660,14 @@ static int hist_impl(dc_ctx *c, const uint8_t *d_in, uint64_t n, uint64_t *d_his
     if (!c || !d_hist || (n && !d_in)) return DC_E_ARG;
     if (((uintptr_t)d_in) & 15) return DC_E_ARG;
     const uint64_t nb = nblocks_of(n);
-    if (ensure((void **)&c->d_bh, &c->bh_cap, (nb ? nb : 1) * 256 * sizeof(uint16_t))) return DC_E_HIP;
+    if (ensure(c->ws.bh, (nb ? nb : 1) * 256 * sizeof(uint16_t))) return DC_E_HIP;
     c->hist_in = d_in;
     c->hist_n = n;
     c->hist_fe = fe;
     c->plan_ok = false;
     if (fe) {   // n >= 2 (dc_small_huff_plan)
         const uint64_t grid = nb < 512u ? nb : 512u;
-        LAUNCH(c, "fe_hist_blocks", (k_hist_blocks<1, true>), grid, 256, d_in, n, nb, c->d_bh, d_hist,
+        LAUNCH(c, "fe_hist_blocks", (k_hist_blocks<1, true>), grid, 256, d_in, n, nb, c->ws.bh, d_hist,
                reinterpret_cast<uint64_t *>(c->d_hflag), c->d_hflag + 512, c->d_hloc, fuse, shard);
         return DC_OK;
     }
@@ -6690,10 +6686,10 @@ static int hist_impl(dc_ctx *c, const uint8_t *d_in, uint64_t n, uint64_t *d_his
     uint64_t *const hacc = reinterpret_cast<uint64_t *>(c->d_hflag);
     uint32_t *const hdone = c->d_hflag + 512;
     if (c->opt_hist_pf == 1)
-        LAUNCH(c, "hist_blocks", k_hist_blocks<1>, grid, 256, d_in, n, nb, c->d_bh, d_hist, hacc, hdone, c->d_hloc, fuse);
+        LAUNCH(c, "hist_blocks", k_hist_blocks<1>, grid, 256, d_in, n, nb, c->ws.bh, d_hist, hacc, hdone, c->d_hloc, fuse);
     else if (c->opt_hist_pf == 3)
-        LAUNCH(c, "hist_blocks", k_hist_blocks<3>, grid, 256, d_in, n, nb, c->d_bh, d_hist, hacc, hdone, c->d_hloc, fuse);
-    else LAUNCH(c, "hist_blocks", k_hist_blocks<2>, grid, 256, d_in, n, nb, c->d_bh, d_hist, hacc, hdone, c->d_hloc, fuse);
+        LAUNCH(c, "hist_blocks", k_hist_blocks<3>, grid, 256, d_in, n, nb, c->ws.bh, d_hist, hacc, hdone, c->d_hloc, fuse);
+    else LAUNCH(c, "hist_blocks", k_hist_blocks<2>, grid, 256, d_in, n, nb, c->ws.bh, d_hist, hacc, hdone, c->d_hloc, fuse);
     return DC_OK;
 }
 
@@ -6747,12 +6743,29 @@ int dc_huff_table_lengths(dc_ctx *c, const int32_t *d_len, int M, int nary, dc_d
 
 int dc_huff_table_status(dc_ctx *c, const dc_dtable *d_table, int32_t *max_bits)
 {
-    int32_t v[2];
-    HIPCHK(hipMemcpyAsync(v, &d_table->max_bits, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(v + 1, &d_table->status, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (max_bits) *max_bits = v[0];
-    return v[1];
+    int32_t bits = 0, status = 0;
+    if (read_back2(c, &d_table->max_bits, &bits, &d_table->status, &status)) return DC_E_HIP;
+    if (max_bits) *max_bits = bits;
+    return status;
+}
+
+// a plan of this context's last histogram under d_table is on the stream, its total at d_total_bits
+static void plan_made(dc_ctx *c, const dc_dtable *d_table, uint64_t *d_total_bits)
+{
+    c->plan_table = d_table;
+    c->plan_total = d_total_bits;
+    c->plan_ok = true;
+}
+// ... and is it the plan of this input? (fe_wrong: the caller's test of hist_fe, false where it makes none)
+static bool plan_is_of(const dc_ctx *c, const uint8_t *d_in, uint64_t n, bool fe_wrong)
+{
+    return d_in == c->hist_in && n == c->hist_n && !fe_wrong && c->plan_ok && c->plan_total;
+}
+// the workgroups of the pack kernels beside workgroup 0: a pair of blocks each, or DC_OPT_PACK_GRID
+static uint64_t pack_grid(const dc_ctx *c, uint64_t nb)
+{
+    const uint64_t gmax = c->opt_pack_grid ? c->opt_pack_grid : (nb + 1) / 2;
+    return nb < gmax ? nb : gmax;
 }
 
 static int *plan_err(dc_ctx *c) { return c->d_errp + 4 * (c->gen_p & 31u); }
@@ -6770,9 +6783,7 @@ int dc_huff_plan(dc_ctx *c, const dc_dtable *d_table, uint64_t *d_total_bits)
     // launches first (plan_offsets: k_block_local + k_block_final_wide)
     LAUNCH(c, "plan_total", k_plan_total, 1, 256, (const uint64_t *)c->d_hloc, d_table, d_total_bits, plan_err(c),
            plan_err_next(c));
-    c->plan_table = d_table;
-    c->plan_total = d_total_bits;
-    c->plan_ok = true;
+    plan_made(c, d_table, d_total_bits);
     return DC_OK;
 }
 
@@ -6786,9 +6797,19 @@ int dc_huff_table_plan(dc_ctx *c, const uint64_t *d_hist, int M, int nary, dc_dt
     // launch, the payload bits of THIS context's last histogram under it (huff_table_body's plan)
     LAUNCH(c, "huff_table", k_huff_table, 1, 256, d_hist, 1, (const int32_t *)nullptr, M, nary, d_table,
            (dc_tree *)nullptr, (const uint64_t *)c->d_hloc, d_total_bits, plan_err(c), plan_err_next(c));
-    c->plan_table = d_table;
-    c->plan_total = d_total_bits;
-    c->plan_ok = true;
+    plan_made(c, d_table, d_total_bits);
+    return DC_OK;
+}
+
+// histogram (fe: of the C5 front-end's output), table and plan in one launch: dc_huff_encode_plan, dc_small_huff_plan
+static int fused_plan(dc_ctx *c, const uint8_t *d_in, uint64_t n, int M, int nary, uint64_t *d_hist, dc_dtable *d_table,
+                      uint64_t *d_total_bits, bool fe)
+{
+    ++c->gen_p;
+    table_written(c);
+    const int r = hist_impl(c, d_in, n, d_hist, HistFuse{d_table, M, nary, d_total_bits, plan_err(c), plan_err_next(c)}, fe);
+    if (r != DC_OK) { --c->gen_p; return r; }
+    plan_made(c, d_table, d_total_bits);
     return DC_OK;
 }
 
@@ -6796,15 +6817,7 @@ int dc_huff_encode_plan(dc_ctx *c, const uint8_t *d_in, uint64_t n, int M, int n
                         dc_dtable *d_table, uint64_t *d_total_bits)
 {
     if (!c || !d_table || !d_total_bits || M < 0 || M >= DC_MAX_SYMS || nary < 2 || nary > 256) return DC_E_ARG;
-    ++c->gen_p;
-    table_written(c);
-    const int r = hist_impl(c, d_in, n, d_hist,
-                            HistFuse{d_table, M, nary, d_total_bits, plan_err(c), plan_err_next(c)});
-    if (r != DC_OK) { --c->gen_p; return r; }
-    c->plan_table = d_table;
-    c->plan_total = d_total_bits;
-    c->plan_ok = true;
-    return DC_OK;
+    return fused_plan(c, d_in, n, M, nary, d_hist, d_table, d_total_bits, false);
 }
 
 // ---- length-limited tables (dc_gpu.h "Length-limited tables"): the twins of the four calls
@@ -6850,9 +6863,7 @@ int dc_huff_table_plan_limit(dc_ctx *c, const uint64_t *d_hist, int M, int nary,
     table_written(c);
     LAUNCH(c, "huff_table_limit", k_huff_table_limit, 1, 256, d_hist, 1, M, nary, max_digits, d_table,
            (const uint64_t *)c->d_hloc, d_total_bits, plan_err(c), plan_err_next(c));
-    c->plan_table = d_table;
-    c->plan_total = d_total_bits;
-    c->plan_ok = true;
+    plan_made(c, d_table, d_total_bits);
     return DC_OK;
 }
 
@@ -6865,51 +6876,50 @@ int dc_huff_encode_plan_limit(dc_ctx *c, const uint8_t *d_in, uint64_t n, int M,
     // the histogram as dc_huff_hist launches it (its last workgroup builds no table), then the
     // capped table and the plan of that histogram in one launch: the histogram kernels stay as
     // they are, at the price of one launch more than the uncapped call
-    const int r = dc_huff_hist(c, d_in, n, d_hist);
-    if (r != DC_OK) return r;
+    if (const int r = dc_huff_hist(c, d_in, n, d_hist)) return r;
     return dc_huff_table_plan_limit(c, (const uint64_t *)c->d_hloc, M, nary, max_digits, d_table, d_total_bits);
 }
 
 // The per-block exclusive bit offsets of the last histogram's input under c->plan_table into
-// c->d_off (nblocks + 1 entries), and with d_words set the zeroed block-boundary words the
+// c->ws.off (nblocks + 1 entries), and with d_words set the zeroed block-boundary words the
 // pack OR-merges into: two launches (one more above PLAN_MAX_WG workgroups of blocks)
 // With sl32 set (C5 fused front-end, k_fe_pack): also the symbol index of each block's first
-// symbol into c->d_msym, and the sync-length dwords of the chunks spanning block boundaries
+// symbol into c->ws.msym, and the sync-length dwords of the chunks spanning block boundaries
 // zeroed (S = 1 << slog); one plan launch pair as well, at most PLAN_MAX_WG workgroups.
 static int plan_offsets(dc_ctx *c, int *err, int *err_next, uint64_t bit_base, const uint64_t *d_base,
                         uint32_t *d_words, uint64_t words_cap, uint32_t *sl32 = nullptr, uint32_t slog = 0,
                         const int64_t *shard = nullptr, uint32_t *gl32 = nullptr)
 {
     const uint64_t nb = nblocks_of(c->hist_n);
-    if (ensure((void **)&c->d_off, &c->off_cap, (nb + 1) * sizeof(uint64_t))) return DC_E_HIP;
+    if (ensure(c->ws.off, (nb + 1) * sizeof(uint64_t))) return DC_E_HIP;
     if (nb == 0) {
         if (sl32) return DC_E_ARG;
-        HIPCHK(hipMemsetAsync(c->d_off, 0, sizeof(uint64_t), c->stream));
+        HIPCHK(hipMemsetAsync(c->ws.off, 0, sizeof(uint64_t), c->stream));
         return DC_OK;
     }
     const uint64_t nwg = (nb + PLAN_WG_BLOCKS - 1) / PLAN_WG_BLOCKS;
     if (nwg <= PLAN_MAX_WG) {
-        if (ensure((void **)&c->d_plan, &c->plan_cap, 2 * (nb + nwg + 64) * sizeof(uint32_t))) return DC_E_HIP;
-        uint32_t *loc = c->d_plan, *tot = c->d_plan + nb + 32;
+        if (ensure(c->ws.plan, 2 * (nb + nwg + 64) * sizeof(uint32_t))) return DC_E_HIP;
+        uint32_t *loc = c->ws.plan, *tot = c->ws.plan + nb + 32;
         uint32_t *lcnt = nullptr, *wgcnt = nullptr;
         if (sl32) {
-            if (ensure((void **)&c->d_msym, &c->msym_cap, (nb + 1) * sizeof(uint64_t))) return DC_E_HIP;
-            lcnt = c->d_plan + nb + nwg + 64;
+            if (ensure(c->ws.msym, (nb + 1) * sizeof(uint64_t))) return DC_E_HIP;
+            lcnt = c->ws.plan + nb + nwg + 64;
             wgcnt = lcnt + nb + 32;
         }
-        LAUNCH(c, "block_bits", k_block_local, nwg, 256, (const uint16_t *)c->d_bh, nb, c->plan_table, loc, tot, err,
+        LAUNCH(c, "block_bits", k_block_local, nwg, 256, (const uint16_t *)c->ws.bh, nb, c->plan_table, loc, tot, err,
                lcnt, wgcnt);
         LAUNCH(c, "block_scan", k_block_final_wide, nwg, 256, (const uint32_t *)loc, (const uint32_t *)tot, nb,
-               (uint32_t)nwg, c->d_off, c->d_meta + 15, err_next, bit_base, d_base, d_words, words_cap,
-               (const uint32_t *)lcnt, (const uint32_t *)wgcnt, c->d_msym, sl32, slog, shard, gl32);
+               (uint32_t)nwg, c->ws.off, c->d_meta + 15, err_next, bit_base, d_base, d_words, words_cap,
+               (const uint32_t *)lcnt, (const uint32_t *)wgcnt, c->ws.msym, sl32, slog, shard, gl32);
     } else if (sl32) {
         return DC_E_ARG;
     } else {
-        LAUNCH(c, "block_bits", k_block_bits, (nb + 3) / 4, 256, (const uint16_t *)c->d_bh, nb, c->plan_table,
-               c->d_off, err);
-        LAUNCH(c, "block_scan", k_block_scan, 1, 1024, c->d_off, nb, c->d_meta + 15, err_next);
+        LAUNCH(c, "block_bits", k_block_bits, (nb + 3) / 4, 256, (const uint16_t *)c->ws.bh, nb, c->plan_table,
+               c->ws.off, err);
+        LAUNCH(c, "block_scan", k_block_scan, 1, 1024, c->ws.off, nb, c->d_meta + 15, err_next);
         if (d_words)
-            LAUNCH(c, "zero_bounds", k_zero_bounds, (nb + 1 + 255) / 256, 256, (const uint64_t *)c->d_off, nb, bit_base,
+            LAUNCH(c, "zero_bounds", k_zero_bounds, (nb + 1 + 255) / 256, 256, (const uint64_t *)c->ws.off, nb, bit_base,
                    d_base, d_words, words_cap);
     }
     return DC_OK;
@@ -6925,11 +6935,7 @@ int dc_huff_plan_offsets(dc_ctx *c, uint64_t *h_off, uint64_t max_entries, uint6
     int *const scratch_err = c->d_err + 12;   // not a plan slot: the flags of the real plan stay
     const int r = plan_offsets(c, scratch_err, scratch_err, 0, nullptr, nullptr, 0);
     if (r != DC_OK) return r;
-    if (k) {
-        HIPCHK(hipMemcpyAsync(h_off, c->d_off, k * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-    }
-    return DC_OK;
+    return dc_memcpy_d2h(c, h_off, c->ws.off, k * sizeof(uint64_t));
 }
 
 int dc_huff_block_hist(dc_ctx *c, uint16_t *h_bh, uint64_t max_entries)
@@ -6937,7 +6943,7 @@ int dc_huff_block_hist(dc_ctx *c, uint16_t *h_bh, uint64_t max_entries)
     if (!c || !c->hist_n) return DC_E_STATE;
     const uint64_t nb = nblocks_of(c->hist_n) * 256;
     const uint64_t k = nb < max_entries ? nb : max_entries;
-    HIPCHK(hipMemcpyAsync(h_bh, c->d_bh, k * sizeof(uint16_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(h_bh, c->ws.bh, k * sizeof(uint16_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     return DC_OK;
 }
@@ -6948,17 +6954,15 @@ uint64_t dc_huff_words_needed(uint64_t bit_base, uint64_t total_bits)
 }
 
 static bool sync_ok(uint32_t S) { return S >= 16 && S <= DC_SYNC_MAX && (S & (S - 1)) == 0; }
-
 uint64_t dc_huff_sync_chunks(uint64_t n, uint32_t S) { return S ? (n + S - 1) / S : 0; }
 uint64_t dc_huff_sync_groups(uint64_t n, uint32_t S) { return (dc_huff_sync_chunks(n, S) + DC_SYNC_GROUP - 1) / DC_SYNC_GROUP; }
-
 
 static int pack_impl(dc_ctx *c, const uint8_t *d_in, uint64_t n, const dc_dtable *d_table, uint64_t bit_base,
                      const uint64_t *d_base, uint32_t *d_words, uint64_t words_cap, uint64_t *d_sync_base,
                      uint16_t *d_sync_len, uint32_t sync_syms)
 {
     if (!c || !d_table || !d_words) return DC_E_ARG;
-    if (d_in != c->hist_in || n != c->hist_n || c->hist_fe || !c->plan_ok || !c->plan_total) return DC_E_STATE;
+    if (!plan_is_of(c, d_in, n, c->hist_fe)) return DC_E_STATE;
     if ((d_sync_base != nullptr) != (d_sync_len != nullptr)) return DC_E_ARG;
     if (d_sync_len && !sync_ok(sync_syms)) return DC_E_ARG;
     const uint64_t nb = nblocks_of(n);
@@ -6972,39 +6976,35 @@ static int pack_impl(dc_ctx *c, const uint8_t *d_in, uint64_t n, const dc_dtable
         (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c->device);
         const uint64_t gmax = c->opt_pack_grid ? c->opt_pack_grid : (uint64_t)ncu * 4;
         const uint64_t grid = nb < gmax ? nb : gmax;
-        LAUNCH(c, "huff_pack", k_huff_pack<true>, grid + 1, 256, d_in, n, d_table, (const uint64_t *)c->d_off, bit_base,
+        LAUNCH(c, "huff_pack", k_huff_pack<true>, grid + 1, 256, d_in, n, d_table, (const uint64_t *)c->ws.off, bit_base,
                d_base, d_words, d_sync_base, d_sync_len, sync_syms, nb, words_cap, plan_err(c), 1);
     } else if (c->opt_pack_block == 6) {   // A/B: one code-table read per byte (k_huff_pack_fold)
-        const uint64_t gmax = c->opt_pack_grid ? c->opt_pack_grid : (nb + 1) / 2;
-        const uint64_t grid = nb < gmax ? nb : gmax;
-        LAUNCH(c, "huff_pack", k_huff_pack_fold, grid + 1, 256, d_in, n, d_table, (const uint64_t *)c->d_off, bit_base,
+        LAUNCH(c, "huff_pack", k_huff_pack_fold, pack_grid(c, nb) + 1, 256, d_in, n, d_table, (const uint64_t *)c->ws.off, bit_base,
                d_base, d_words, d_sync_base, d_sync_len, sync_syms, nb, words_cap, plan_err(c), 1);
     } else if (c->opt_pack_block == 5) {   // A/B: a half-block stage, more workgroups per CU (k_huff_pack_half)
-        LAUNCH(c, "huff_pack", k_huff_pack_half, (nb + 1) / 2, 256, d_in, n, d_table, (const uint64_t *)c->d_off,
+        LAUNCH(c, "huff_pack", k_huff_pack_half, (nb + 1) / 2, 256, d_in, n, d_table, (const uint64_t *)c->ws.off,
                bit_base, d_base, d_words, d_sync_base, d_sync_len, sync_syms, nb, words_cap, plan_err(c));
     } else if (c->opt_pack_block == 4) {   // A/B: the next block in flight by LDS-DMA (k_huff_pack_dma)
         int ncu = 256;
         (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c->device);
         const uint64_t grid = (uint64_t)ncu * PKD_WG_PER_CU;
         LAUNCH(c, "huff_pack", k_huff_pack_dma, (nb < grid ? nb : grid) + 1, 256, d_in, n, d_table,
-               (const uint64_t *)c->d_off, bit_base, d_base, d_words, d_sync_base, d_sync_len, sync_syms, nb, words_cap,
+               (const uint64_t *)c->ws.off, bit_base, d_base, d_words, d_sync_base, d_sync_len, sync_syms, nb, words_cap,
                plan_err(c), 1);
     } else if ((((uintptr_t)d_words) & 15) == 0 && c->opt_pack_block >= 2 && n >= 1024) {   // A/B: 0.386 vs 0.380 ms
-        if (ensure((void **)&c->d_scr, &c->scr_cap, (size_t)D8_SCRATCH_WAVES * D8_WSCR)) return DC_E_HIP;   // trash rows
+        if (ensure(c->ws.scr, (size_t)D8_SCRATCH_WAVES * D8_WSCR)) return DC_E_HIP;   // trash rows
         // one wave per range of bpw blocks (k_huff_pack_w): ~PW_WAVES waves, 4 per workgroup,
         // + workgroup 0: the decoder tables (k_huff_table leaves them to the pack's idle CU time)
         const uint64_t bpw = c->opt_pack_grid ? c->opt_pack_grid : (nb + PW_WAVES - 1) / PW_WAVES;
         const uint64_t waves = (nb + bpw - 1) / bpw;
-        LAUNCH(c, "huff_pack", k_huff_pack_w, (waves + 3) / 4 + 1, 256, d_in, n, d_table, (const uint64_t *)c->d_off,
+        LAUNCH(c, "huff_pack", k_huff_pack_w, (waves + 3) / 4 + 1, 256, d_in, n, d_table, (const uint64_t *)c->ws.off,
                bit_base, d_base, d_words, d_sync_base, d_sync_len, sync_syms, nb, words_cap, plan_err(c), 1,
-               (uint32_t)bpw, (uint8_t *)c->d_scr, c->opt_pack_block == 3 ? 1 : 0);
+               (uint32_t)bpw, c->ws.scr.get(), c->opt_pack_block == 3 ? 1 : 0);
     } else
 #endif
     {
         // two blocks per workgroup (grid-stride) + workgroup 0: the decoder tables
-        const uint64_t gmax = c->opt_pack_grid ? c->opt_pack_grid : (nb + 1) / 2;
-        const uint64_t grid = nb < gmax ? nb : gmax;
-        LAUNCH(c, "huff_pack", k_huff_pack<>, grid + 1, 256, d_in, n, d_table, (const uint64_t *)c->d_off, bit_base,
+        LAUNCH(c, "huff_pack", k_huff_pack<>, pack_grid(c, nb) + 1, 256, d_in, n, d_table, (const uint64_t *)c->ws.off, bit_base,
                d_base, d_words, d_sync_base, d_sync_len, sync_syms, nb, words_cap, plan_err(c), 1);
     }
     dec_tables_built(c, d_table);   // workgroup 0 built the decoder tables
@@ -7032,15 +7032,7 @@ int dc_small_huff_plan(dc_ctx *c, const uint8_t *d_in, uint64_t n, int M, int na
 {
     if (!c || !d_table || !d_total_bits || !d_hist || M < 255 || M >= DC_MAX_SYMS || nary < 2 || nary > 256) return DC_E_ARG;
     if (n < 2) return DC_E_FALLBACK;   // the front-end output of < 2 bytes is LITERAL
-    ++c->gen_p;
-    table_written(c);
-    const int r = hist_impl(c, d_in, n, d_hist, HistFuse{d_table, M, nary, d_total_bits, plan_err(c), plan_err_next(c)},
-                            true);
-    if (r != DC_OK) { --c->gen_p; return r; }
-    c->plan_table = d_table;
-    c->plan_total = d_total_bits;
-    c->plan_ok = true;
-    return DC_OK;
+    return fused_plan(c, d_in, n, M, nary, d_hist, d_table, d_total_bits, true);
 }
 
 int dc_small_huff_pack_async(dc_ctx *c, const uint8_t *d_in, uint64_t n, const dc_dtable *d_table, uint64_t bit_base,
@@ -7049,15 +7041,13 @@ int dc_small_huff_pack_async(dc_ctx *c, const uint8_t *d_in, uint64_t n, const d
 {
     if (!c || !d_table || !d_words || !d_sync_base || !d_sync_len || !sync_ok(sync_syms)) return DC_E_ARG;
     if (((uintptr_t)d_sync_len) & 3) return DC_E_ARG;
-    if (d_in != c->hist_in || n != c->hist_n || !c->hist_fe || !c->plan_ok || !c->plan_total) return DC_E_STATE;
+    if (!plan_is_of(c, d_in, n, !c->hist_fe)) return DC_E_STATE;
     const uint64_t nb = nblocks_of(n);
     const int r = plan_offsets(c, plan_err(c), plan_err_next(c), bit_base, nullptr, d_words, words_cap,
                                reinterpret_cast<uint32_t *>(d_sync_len), (uint32_t)__builtin_ctz(sync_syms));
     if (r != DC_OK) return r;
-    const uint64_t gmax = c->opt_pack_grid ? c->opt_pack_grid : (nb + 1) / 2;
-    const uint64_t grid = nb < gmax ? nb : gmax;
-    LAUNCH(c, "fe_pack", k_fe_pack<false>, grid + 1, 256, d_in, n, d_table, (const uint64_t *)c->d_off,
-           (const uint64_t *)c->d_msym, bit_base, d_words, d_sync_base, d_sync_len, sync_syms, nb, words_cap,
+    LAUNCH(c, "fe_pack", k_fe_pack<false>, pack_grid(c, nb) + 1, 256, d_in, n, d_table, (const uint64_t *)c->ws.off,
+           (const uint64_t *)c->ws.msym, bit_base, d_words, d_sync_base, d_sync_len, sync_syms, nb, words_cap,
            plan_err(c), 1, (const int64_t *)nullptr, (uint64_t *)nullptr, (uint16_t *)nullptr);
     dec_tables_built(c, d_table);
     return DC_OK;
@@ -7086,17 +7076,15 @@ int dc_small_huff_shard_pack_async(dc_ctx *c, const uint8_t *d_in, uint64_t n, c
         !sync_ok(sync_syms))
         return DC_E_ARG;
     if ((((uintptr_t)d_sync_len) & 3) || (((uintptr_t)d_gsync_len) & 3)) return DC_E_ARG;
-    if (d_in != c->hist_in || n != c->hist_n || !c->hist_fe || !c->plan_ok || !c->plan_total) return DC_E_STATE;
+    if (!plan_is_of(c, d_in, n, !c->hist_fe)) return DC_E_STATE;
     const uint64_t nb = nblocks_of(n);
     const uint32_t slog = (uint32_t)__builtin_ctz(sync_syms);
     const int r = plan_offsets(c, plan_err(c), plan_err_next(c), 0, reinterpret_cast<const uint64_t *>(d_shard),
                                d_words, words_cap, reinterpret_cast<uint32_t *>(d_sync_len), slog, d_shard,
                                reinterpret_cast<uint32_t *>(d_gsync_len));
     if (r != DC_OK) return r;
-    const uint64_t gmax = c->opt_pack_grid ? c->opt_pack_grid : (nb + 1) / 2;
-    const uint64_t grid = nb < gmax ? nb : gmax;
-    LAUNCH(c, "fe_pack", k_fe_pack<true>, grid + 1, 256, d_in, n, d_table, (const uint64_t *)c->d_off,
-           (const uint64_t *)c->d_msym, (uint64_t)0, d_words, d_sync_base, d_sync_len, sync_syms, nb, words_cap,
+    LAUNCH(c, "fe_pack", k_fe_pack<true>, pack_grid(c, nb) + 1, 256, d_in, n, d_table, (const uint64_t *)c->ws.off,
+           (const uint64_t *)c->ws.msym, (uint64_t)0, d_words, d_sync_base, d_sync_len, sync_syms, nb, words_cap,
            plan_err(c), 1, d_shard, d_gsync_base, d_gsync_len);
     dec_tables_built(c, d_table);
     return DC_OK;
@@ -7105,10 +7093,8 @@ int dc_small_huff_shard_pack_async(dc_ctx *c, const uint8_t *d_in, uint64_t n, c
 int dc_small_huff_symbols(dc_ctx *c, uint64_t *h_m)
 {
     if (!c || !h_m) return DC_E_ARG;
-    if (!c->hist_fe || !c->d_msym || !c->hist_n) return DC_E_STATE;
-    HIPCHK(hipMemcpyAsync(h_m, c->d_msym + nblocks_of(c->hist_n), sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return DC_OK;
+    if (!c->hist_fe || !c->ws.msym || !c->hist_n) return DC_E_STATE;
+    return read_back(c, c->ws.msym + nblocks_of(c->hist_n), h_m);
 }
 
 uint32_t dc_huff_plan_gen(dc_ctx *c) { return c ? c->gen_p : 0u; }
@@ -7126,8 +7112,7 @@ int dc_huff_pack_status_gen(dc_ctx *c, const dc_dtable *d_table, uint32_t gen)
     // a plan more than 30 plans back has lost its flags
     if ((uint32_t)(c->gen_p - gen) > 30u) return DC_E_STATE;
     int v[3] = {0, 0, 0};
-    HIPCHK(hipMemcpyAsync(v, c->d_errp + 4 * (gen & 31u), 3 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    if (read_back(c, c->d_errp + 4 * (gen & 31u), v, 3)) return DC_E_HIP;
     if (v[0]) {
         const int st = dc_huff_table_status(c, d_table, nullptr);
         return st ? st : DC_E_NOCODE;
@@ -7141,29 +7126,22 @@ int dc_huff_pack(dc_ctx *c, const uint8_t *d_in, uint64_t n, const dc_dtable *d_
                  uint32_t sync_syms)
 {
     if (!c || !d_table || !d_words) return DC_E_ARG;
-    if (d_in != c->hist_in || n != c->hist_n || !c->plan_ok || !c->plan_total) return DC_E_STATE;
+    if (!plan_is_of(c, d_in, n, false)) return DC_E_STATE;   // (the one pack that makes no test of hist_fe)
     if ((d_sync_base != nullptr) != (d_sync_len != nullptr)) return DC_E_ARG;
     if (d_sync_len && !sync_ok(sync_syms)) return DC_E_ARG;
     // plan errors (a byte without a code) are checked here: host read of one int
     int err = 0;
-    HIPCHK(hipMemcpyAsync(c->h_pinned, plan_err(c), sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(c->h_pinned + 1, c->plan_total, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    err = *(int *)c->h_pinned;
+    uint64_t total = 0;
+    if (const int r = read_back2(c, plan_err(c), &err, c->plan_total, &total)) return r;
     if (err) {
         const int st = dc_huff_table_status(c, d_table, nullptr);
         return st ? st : DC_E_NOCODE;
     }
-    const uint64_t total = c->h_pinned[1];
     if (dc_huff_words_needed(bit_base, total) > words_cap) return DC_E_CAPACITY;
     return dc_huff_pack_async(c, d_in, n, d_table, bit_base, d_words, words_cap, d_sync_base, d_sync_len, sync_syms);
 }
 
-uint32_t dc_huff_default_sync(uint64_t n)
-{
-    (void)n;
-    return 64;
-}
+uint32_t dc_huff_default_sync(uint64_t) { return 64; }
 
 uint32_t dc_huff_choose_sync(uint64_t n, uint64_t total_bits)
 {
@@ -7172,6 +7150,17 @@ uint32_t dc_huff_choose_sync(uint64_t n, uint64_t total_bits)
     if (n == 0) return 64;
     const double avg = (double)total_bits / (double)n;
     return (64.0 * 64.0 * avg / 8.0 <= 4200.0) ? 64u : 32u;
+}
+
+// What the three decode entry points begin with: the call's error slot (cleared by the decode
+// before; it clears the next one) and the decoder tables, unless this context's last pack built
+// them for this table (no launch then; a table rebuilt elsewhere since reads dec_ready 0 in the
+// decoder: a stream error)
+static int dec_begin(dc_ctx *c, const dc_dtable *d_table)
+{
+    ++c->gen_d;
+    if (!dec_tables_fresh(c, d_table)) LAUNCH(c, "dec_tables", k_dec_tables, 1, 256, const_cast<dc_dtable *>(d_table), dec_err(c));
+    return DC_OK;
 }
 
 // d_gexp (C5, dc_small_huff_decode): symbols >= 0x80 per group of 64 chunks, from the fast
@@ -7187,11 +7176,8 @@ static int decode_impl(dc_ctx *c, const uint32_t *d_words, uint64_t bit_base, co
     if (n == 0) return DC_OK;
     if (words < 4) return DC_E_ARG;
     const uint64_t groups = dc_huff_sync_groups(n, S);
-    ++c->gen_d;   // this decode's error slot (cleared by the decode before; it clears the next one)
+    if (const int r = dec_begin(c, d_table)) return r;
     int *const derr = dec_err(c), *const derr_next = dec_err_next(c);
-    // the decoder tables, unless this context's last pack built them for this table (no launch
-    // then; a table rebuilt elsewhere since reads dec_ready 0 in the decoder: a stream error)
-    if (!dec_tables_fresh(c, d_table)) LAUNCH(c, "dec_tables", k_dec_tables, 1, 256, const_cast<dc_dtable *>(d_table), derr);
     const bool fast8 = S == 64 && n < (1ull << 37) && words < (1ull << 31) && !c->opt_decode_general;
     if (d_gexp && (!fast8 || c->opt_decode_variant != 0)) return DC_E_ARG;   // (k_huff_decode9 writes no counts)
     if (fast8) {
@@ -7199,32 +7185,29 @@ static int decode_impl(dc_ctx *c, const uint32_t *d_words, uint64_t bit_base, co
         // LDS (the 8 x 4 split measured 0.89 vs 0.70 ms on 1 GiB C2: spills)
         const uint32_t spct = c->opt_d8_static;   // clamped to 0..100 by dc_ctx_set_option
         const uint64_t tuples = (groups + 1) / 2;   // 2 chains (groups) per wave
-        if (ensure((void **)&c->d_fix, &c->fix_cap, (2 * groups + 64) * sizeof(uint64_t)) ||   // masks, first starts
-            ensure((void **)&c->d_fixpos, &c->fixpos_cap, (groups * 64 + 64) * sizeof(uint64_t)))
+        if (ensure(c->ws.fix, (2 * groups + 64) * sizeof(uint64_t)) ||   // masks, first starts
+            ensure(c->ws.fixpos, (groups * 64 + 64) * sizeof(uint64_t)))
             return DC_E_HIP;
-        if (ensure((void **)&c->d_scr, &c->scr_cap, (size_t)D8_SCRATCH_WAVES * D8_WSCR)) return DC_E_HIP;
-#define D8_LAUNCH(NW_, NC_)                                                                                   \
-        LAUNCH(c, "huff_decode", (k_huff_decode8<NW_, NC_>), (tuples + NW_ - 1) / NW_ < 256 ? (tuples + NW_ - 1) / NW_ : 256, \
-               NW_ * 64, d_words, bit_base, d_base, d_sync_base, d_sync_len, n, words, d_table, d_out, derr,       \
-               c->d_queue, spct, (uint64_t *)c->d_fix, (uint64_t *)c->d_fixpos, (uint8_t *)c->d_scr)
+        if (ensure(c->ws.scr, (size_t)D8_SCRATCH_WAVES * D8_WSCR)) return DC_E_HIP;
 #ifdef DC_AB_KERNELS
         if (c->opt_decode_variant == 1) {   // multi-symbol lookups, one group per wave
             LAUNCH(c, "huff_decode", k_huff_decode9<12>, groups < 256 * 12 ? (groups + 11) / 12 : 256, 12 * 64,
                    d_words, bit_base, d_base, d_sync_base, d_sync_len, n, words, d_table, d_out, derr, c->d_queue,
-                   spct, (uint64_t *)c->d_fix, (uint64_t *)c->d_fixpos, (uint8_t *)c->d_scr);
+                   spct, c->ws.fix.get(), c->ws.fixpos.get(), c->ws.scr.get());
         } else
 #endif
         if (d_gexp) {   // (C5) with the symbols >= 0x80 per group
             LAUNCH(c, "huff_decode", (k_huff_decode8<11, 2, true>), (tuples + 10) / 11 < 256 ? (tuples + 10) / 11 : 256,
                    11 * 64, d_words, bit_base, d_base, d_sync_base, d_sync_len, n, words, d_table, d_out, derr,
-                   c->d_queue, spct, (uint64_t *)c->d_fix, (uint64_t *)c->d_fixpos, (uint8_t *)c->d_scr, d_gexp);
+                   c->d_queue, spct, c->ws.fix.get(), c->ws.fixpos.get(), c->ws.scr.get(), d_gexp);
         } else {   // one code per lookup, 11 waves x 2 chains (the 15-bit table takes 64 KiB of LDS)
-            D8_LAUNCH(11, 2);
+            LAUNCH(c, "huff_decode", (k_huff_decode8<11, 2>), (tuples + 10) / 11 < 256 ? (tuples + 10) / 11 : 256, 11 * 64,
+                   d_words, bit_base, d_base, d_sync_base, d_sync_len, n, words, d_table, d_out, derr, c->d_queue, spct,
+                   c->ws.fix.get(), c->ws.fixpos.get(), c->ws.scr.get());
         }
-#undef D8_LAUNCH
         c->last_groups = groups;
         LAUNCH(c, "huff_decode_fix", k_huff_decode8_fix, 256, D8F_WAVES * 64, d_words, n, words, d_table, d_out,
-               derr, (const uint64_t *)c->d_fix, (const uint64_t *)c->d_fixpos, derr_next, d_gexp);
+               derr, (const uint64_t *)c->ws.fix, (const uint64_t *)c->ws.fixpos, derr_next, d_gexp);
         return DC_OK;
     }
     const uint64_t wgs = (groups + DEC_WAVES - 1) / DEC_WAVES;
@@ -7253,10 +7236,10 @@ int dc_huff_decode_redo_count(dc_ctx *c, uint64_t *count)
 {
     if (!c || !count) return DC_E_ARG;
     *count = 0;
-    if (!c->d_fix || !c->last_groups) return DC_OK;
+    if (!c->ws.fix || !c->last_groups) return DC_OK;
     uint64_t *h = (uint64_t *)malloc(c->last_groups * sizeof(uint64_t));
     if (!h) return DC_E_ARG;
-    const bool ok = hipMemcpyAsync(h, c->d_fix, c->last_groups * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream) ==
+    const bool ok = hipMemcpyAsync(h, c->ws.fix, c->last_groups * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream) ==
                         hipSuccess &&
                     hipStreamSynchronize(c->stream) == hipSuccess;
     if (ok)
@@ -7268,8 +7251,7 @@ int dc_huff_decode_redo_count(dc_ctx *c, uint64_t *count)
 int dc_huff_decode_status(dc_ctx *c)
 {
     int v = 0;
-    HIPCHK(hipMemcpyAsync(&v, dec_err(c), sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    if (read_back(c, dec_err(c), &v)) return DC_E_HIP;
     if (v == RNG_BAD_RANGE) return DC_E_ARG;   // (dc_huff_decode_ranges) only a bad range: the others are decoded
     return v ? DC_E_STREAM : DC_OK;
 }
@@ -7294,11 +7276,10 @@ int dc_huff_decode_ranges(dc_ctx *c, const uint32_t *d_words, uint64_t bit_base,
     if (nranges == 0) return DC_OK;
     if (!d_first || !d_count || !d_out_off || (!d_out && out_cap) || nranges > DC_RANGES_MAX) return DC_E_ARG;
     if (const int r = range_args(c, d_words, words, d_sync_base, d_sync_len, S, d_table)) return r;
-    if (ensure((void **)&c->d_rng, &c->rng_cap, (2 * nranges + 2) * sizeof(uint64_t))) return DC_E_HIP;
-    uint64_t *const items = c->d_rng, *const off = c->d_rng + nranges;
-    ++c->gen_d;   // the error slot, as decode_impl
+    if (ensure(c->ws.rng, (2 * nranges + 2) * sizeof(uint64_t))) return DC_E_HIP;
+    uint64_t *const items = c->ws.rng, *const off = c->ws.rng + nranges;
+    if (const int r = dec_begin(c, d_table)) return r;
     int *const derr = dec_err(c), *const derr_next = dec_err_next(c);
-    if (!dec_tables_fresh(c, d_table)) LAUNCH(c, "dec_tables", k_dec_tables, 1, 256, const_cast<dc_dtable *>(d_table), derr);
     LAUNCH(c, "huff_range_items", k_range_items, (nranges + 255) / 256, 256, d_first, d_count, d_out_off, nranges, n,
            out_cap, S, items, derr);
     LAUNCH(c, "huff_range_scan", k_scan_u64, 1, 1024, (const uint64_t *)items, nranges, off);
@@ -7323,9 +7304,8 @@ int dc_huff_decode_range(dc_ctx *c, const uint32_t *d_words, uint64_t bit_base, 
     if (first > n || count > n - first) return DC_E_ARG;
     if (count && !d_out) return DC_E_ARG;
     if (const int r = range_args(c, d_words, words, d_sync_base, d_sync_len, S, d_table)) return r;
-    ++c->gen_d;
+    if (const int r = dec_begin(c, d_table)) return r;
     int *const derr = dec_err(c), *const derr_next = dec_err_next(c);
-    if (!dec_tables_fresh(c, d_table)) LAUNCH(c, "dec_tables", k_dec_tables, 1, 256, const_cast<dc_dtable *>(d_table), derr);
     const uint32_t glog = (uint32_t)__builtin_ctz(S) + DC_SYNC_GROUP_LOG;
     const uint64_t items = count ? ((first + count - 1) >> glog) - (first >> glog) + 1 : 0;
     const uint64_t wgs = (items + DEC_WAVES - 1) / DEC_WAVES;
@@ -7365,12 +7345,12 @@ static int hbatch_w(int nary)
     return w;
 }
 
-// What every batch call begins with: d_hb sized for `count` segments (the first-failure slot, then
+// What every batch call begins with: ws.hb sized for `count` segments (the first-failure slot, then
 // the plan's payload bytes and chunks per segment) and the slot turned over to "no failure".
 static int hbatch_begin(dc_ctx *c, uint64_t count, unsigned long long **first)
 {
-    if (ensure((void **)&c->d_hb, &c->hb_cap, (2 * count + 2) * sizeof(uint64_t))) return DC_E_HIP;
-    *first = reinterpret_cast<unsigned long long *>(c->d_hb);
+    if (ensure(c->ws.hb, (2 * count + 2) * sizeof(uint64_t))) return DC_E_HIP;
+    *first = reinterpret_cast<unsigned long long *>(c->ws.hb.get());
     HIPCHK(hipMemsetAsync(*first, 0xFF, sizeof(uint64_t), c->stream));
     return DC_OK;
 }
@@ -7383,7 +7363,7 @@ static uint64_t hbatch_grid(const dc_ctx *c, uint64_t work, uint64_t cap)
     return work < cap ? work : cap;
 }
 
-// What the two encodes begin with: 1 (nothing to do), 0 with d_hb sized and the first-failure slot
+// What the two encodes begin with: 1 (nothing to do), 0 with ws.hb sized and the first-failure slot
 // turned over, or an error.
 static int hbatch_encode_begin(dc_ctx *c, const dc_hbatch *b, bool need_lens, const uint64_t *d_in_off, uint64_t count,
                                unsigned long long **first)
@@ -7429,7 +7409,7 @@ static int hbatch_encode_own(dc_ctx *c, const uint8_t *d_in, const uint64_t *d_i
 {
     unsigned long long *first;
     if (const int r = hbatch_encode_begin(c, b, true, d_in_off, count, &first)) return r > 0 ? DC_OK : r;
-    uint64_t *const psize = c->d_hb + 2, *const nch = c->d_hb + 2 + count;
+    uint64_t *const psize = c->ws.hb + 2, *const nch = c->ws.hb + 2 + count;
     const uint64_t g3 = hbatch_grid(c, count, 768), g2 = hbatch_grid(c, count, 512);   // LDS-bound: 3 and 2 per CU
     if (max_digits == 0)
         LAUNCH(c, "hb_plan", k_hb_plan<false>, g3, HB_THREADS, d_in, d_in_off, count, (int)b->n_ary, b->sync_syms, b->d_lens,
@@ -7512,7 +7492,7 @@ int dc_huff_encode_batch_shared(dc_ctx *c, const uint8_t *d_in, const uint64_t *
     if (!d_table) return DC_E_ARG;
     unsigned long long *first;
     if (const int r = hbatch_encode_begin(c, b, false, d_in_off, count, &first)) return r > 0 ? DC_OK : r;
-    uint64_t *const psize = c->d_hb + 2, *const nch = c->d_hb + 2 + count;
+    uint64_t *const psize = c->ws.hb + 2, *const nch = c->ws.hb + 2 + count;
     // the plan's LDS is 288 B (4 workgroups a CU), the pack's stage allows 2
     const uint64_t g4 = hbatch_grid(c, count, 1024), g2 = hbatch_grid(c, count, 512);
     LAUNCH(c, "hbs_plan", k_hbs_plan, g4, HB_THREADS, d_in, d_in_off, count, (int)b->n_ary, b->sync_syms, d_table, b->d_mode,
@@ -7610,23 +7590,19 @@ int dc_huff_table_get_lengths(dc_ctx *c, const dc_dtable *d_table, int32_t *h_le
 {
     if (!c || !d_table || !h_count || max_entries < 0 || (max_entries && !h_lengths)) return DC_E_ARG;
     int32_t M = -1;
-    HIPCHK(hipMemcpyAsync(&M, &d_table->max_symbol_value, sizeof(M), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    if (read_back(c, &d_table->max_symbol_value, &M)) return DC_E_HIP;
     if (M < 0 || M >= DC_MAX_SYMS) return DC_E_ARG;   // not a table the table kernels wrote
     *h_count = M + 1;
     if (max_entries < M + 1) return DC_E_CAPACITY;
-    HIPCHK(hipMemcpyAsync(h_lengths, d_table->lengths, (size_t)(M + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return DC_OK;
+    return dc_memcpy_d2h(c, h_lengths, d_table->lengths, (size_t)(M + 1) * sizeof(int32_t));
 }
 
 int dc_huff_batch_status(dc_ctx *c)
 {
     if (!c) return DC_E_ARG;
-    if (!c->d_hb) return DC_OK;   // no batch call yet
+    if (!c->ws.hb) return DC_OK;   // no batch call yet
     uint64_t v = 0;
-    HIPCHK(hipMemcpyAsync(&v, c->d_hb, sizeof(v), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    if (read_back(c, c->ws.hb.get(), &v)) return DC_E_HIP;
     return v == HB_NO_FAIL ? DC_OK : -(int)(v & 255u);
 }
 
@@ -7661,8 +7637,7 @@ int dc_huff_text_parse_status(dc_ctx *c)
 {
     if (!c) return DC_E_ARG;
     int v = 0;
-    HIPCHK(hipMemcpyAsync(&v, c->d_err + 8, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    if (read_back(c, c->d_err + 8, &v)) return DC_E_HIP;
     return v ? DC_E_STREAM : DC_OK;
 }
 
@@ -7678,114 +7653,172 @@ int dc_huff_base64url(dc_ctx *c, const uint32_t *d_words, uint64_t bit_base, uin
 }  // extern "C"
 
 // ---- byte-stream transducer codecs --------------------------------------------------
-// tiles + scan (from state aux.s_init) + write; h_plan (optional) gets the whole composition
-// (c0, c1, s0, s1) for shard plans; write = false stops after the scan
-// gexp (M_SMALL_DEC only, dc_small_huff_decode): the tile summaries from the decoder's counts
-// (k_small_dec_summ) instead of the counting pass
-template <int M>
-static int fsm_run(dc_ctx *c, const uint8_t *d_in, uint64_t len, uint64_t nelem, uint8_t *d_out, uint64_t *h_len,
-                   const char *name, FsmAux aux = FsmAux{nullptr, 0, 0, 1, 1}, uint64_t *h_plan = nullptr,
-                   bool write = true, const uint32_t *gexp = nullptr, uint64_t ngroups = 0, bool summ_ready = false)
+// A run is fsm_count (the tile summaries and their scan from state aux.s_init), fsm_write (the
+// write launch) and fsm_finish (the read-back and the stream's length): fsm_run does all three,
+// with PLAN_ONLY it stops short of the write, and fsm_write_planned writes what such a plan left.
+
+// The FsmAux of each kind of call: a whole stream (and the small modes); its decode to tokens (a hit
+// as 0x80 | rank); an encoder's shard body, a nybble pending from the shard before (its byte's rank)
+// or none (-1); a decoder's shard body
+static FsmAux aux_whole() { return FsmAux{nullptr, 0, 0, 1, 1, 0, nullptr, nullptr}; }
+static FsmAux aux_tokens() { return FsmAux{nullptr, 0, 0, 1, 1, 1, nullptr, nullptr}; }
+static FsmAux aux_body(int pend_rank, bool is_last)
 {
-    const uint64_t ntiles = SmMode<M>::fast ? sm_ntiles<M>(d_in, FsmOff<M>::v, nelem) : (nelem + FSM_TILE - 1) / FSM_TILE;
+    const uint32_t pend = pend_rank >= 0;
+    return FsmAux{nullptr, pend ? (uint32_t)pend_rank : 0u, pend, is_last ? 1u : 0u, 0, 0, nullptr, nullptr};
+}
+static FsmAux aux_dbody(uint32_t s_in) { return FsmAux{nullptr, 0, s_in, 0, 0, 0, nullptr, nullptr}; }
+// ... and the adaptive encodes: the last mtf_run(ranks)'s step records, per-tile counts and, when the input has elements, ranks
+static FsmAux aux_adaptive(const dc_ctx *c, FsmAux aux, bool ranks)
+{
+    aux.rk = ranks ? c->ws.rk.get() : nullptr;
+    aux.frec = c->ws.mrec;
+    aux.fhead = c->ws.mhead;
+    return aux;
+}
+
+// Where the tile summaries come from: the mode's counting pass, k_mtf_resolve (mtf_run(ranks) left them when the
+// input has elements: `have`), or the Huffman decoder's counts per group (M_SMALL_DEC: k_small_dec_summ)
+struct FsmSumm { bool resolved; const uint32_t *gexp; uint64_t ngroups; };
+static FsmSumm summ_counted() { return FsmSumm{false, nullptr, 0}; }
+static FsmSumm summ_resolved(bool have) { return FsmSumm{have, nullptr, 0}; }
+static FsmSumm summ_decoder(const uint32_t *gexp, uint64_t ngroups) { return FsmSumm{false, gexp, ngroups}; }
+
+// What a run read back (d_meta as k_fsm_scan and the write kernels leave it), and the stream's length
+struct FsmResult {
+    uint64_t count;     // bytes emitted from state aux.s_init
+    uint64_t state;     // exit state: a nybble is pending
+    uint64_t comp[4];   // the composition of the whole input: c0, c1, s0, s1
+    uint64_t type;      // summ_decoder: the stream's type byte as k_small_dec_summ saw it
+    uint64_t total;     // bytes of the stream or body (fsm_finish)
+};
+
+template <int M> static uint64_t fsm_ntiles(const uint8_t *d_in, uint64_t nelem)
+{
+    return SmMode<M>::fast ? sm_ntiles<M>(d_in, FsmOff<M>::v, nelem) : (nelem + FSM_TILE - 1) / FSM_TILE;
+}
+
+// the tile summaries into ws.summ and their scan: entry states in ws.entry, the totals in d_meta
+template <int M>
+static int fsm_count(dc_ctx *c, const uint8_t *d_in, uint64_t len, uint64_t nelem, const char *name, const FsmAux &aux,
+                     const FsmSumm &summ)
+{
+    const uint64_t ntiles = fsm_ntiles<M>(d_in, nelem);
     const uint64_t nt = ntiles ? ntiles : 1;
     const uint64_t ng = (nt + FSM_GROUP - 1) / FSM_GROUP;
-    if (ensure((void **)&c->d_summ, &c->summ_cap, (nt + ng) * sizeof(uint4))) return DC_E_HIP;
-    if (ensure((void **)&c->d_entry, &c->entry_cap, ng * sizeof(uint64_t))) return DC_E_HIP;
-    uint4 *gsum = c->d_summ + nt;
+    if (ensure(c->ws.summ, (nt + ng) * sizeof(uint4))) return DC_E_HIP;
+    if (ensure(c->ws.entry, ng * sizeof(uint64_t))) return DC_E_HIP;
+    uint4 *gsum = c->ws.summ + nt;
     if (ntiles == 0) {
-        // empty: count 0, state unchanged; composition = identity
-        c->h_pinned[0] = 0; c->h_pinned[1] = aux.s_init;
-        c->h_pinned[2] = 0; c->h_pinned[3] = 0; c->h_pinned[4] = 0; c->h_pinned[5] = 1;
-        HIPCHK(hipMemcpyAsync(c->d_meta, c->h_pinned, 6 * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
-        c->h_pinned[6] = aux.s_init;
-        HIPCHK(hipMemcpyAsync(c->d_entry, c->h_pinned + 6, sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
-        uint32_t *idn = reinterpret_cast<uint32_t *>(c->h_pinned + 8);   // identity local composition
-        idn[0] = 0; idn[1] = 0; idn[2] = 0; idn[3] = 1;
-        HIPCHK(hipMemcpyAsync(c->d_summ, idn, sizeof(uint4), hipMemcpyHostToDevice, c->stream));
+        // empty: count 0, state unchanged; composition = identity (and the identity local composition)
+        const uint64_t meta[6] = {0, aux.s_init, 0, 0, 0, 1}, entry = aux.s_init;
+        const uint32_t idn[4] = {0, 0, 0, 1};
+        if (const int r = upload(c, c->d_meta, meta, sizeof(meta), 0)) return r;
+        if (const int r = upload(c, c->ws.entry, &entry, sizeof(entry), 6)) return r;
+        if (const int r = upload(c, c->ws.summ, idn, sizeof(idn), 8)) return r;
         HIPCHK(hipStreamSynchronize(c->stream));
-    } else {
-        if (M == M_SMALL_DEC && gexp)
-            LAUNCH(c, "small_dec_summ", k_small_dec_summ, (ntiles + 255) / 256, 256, gexp, ngroups, d_in, len, ntiles,
-                   c->d_summ, c->d_meta);
-        else if constexpr (SmMode<M>::fast) LAUNCH(c, name, k_small_tiles<M>, ntiles, 256, d_in, len, nelem, c->d_summ);
-        else if (M == M_NYB_ENC && aux.frec && !summ_ready) return DC_E_STATE;   // (ranks with unsettled first touches)
-        else if (summ_ready) {   // (k_mtf_resolve's: the scan below rewrites d_summ in place)
-            if (!c->summ_fresh)
-                HIPCHK(hipMemcpyAsync(c->d_summ, c->d_fraw, ntiles * sizeof(uint4), hipMemcpyDeviceToDevice, c->stream));
-        }
-        else if ((M == M_NYB_ENC && !aux.rk) || M == M_NYB_DEC || M == M_NYB_DBODY)
-            LAUNCH(c, name, k_nyb_tiles<M == M_NYB_DEC ? M_NYB_DEC : M == M_NYB_DBODY ? M_NYB_DBODY : M_NYB_ENC>,
-                   (ntiles + 4 * NYB_TPW - 1) / (4 * NYB_TPW), 256, d_in, len, nelem, ntiles, c->d_summ);
-        else LAUNCH(c, name, k_fsm_tiles<M>, ntiles, 256, d_in, len, nelem, c->d_summ, aux);
-        c->summ_fresh = false;   // (d_summ rewritten in place: no longer the resolver's summaries)
-        LAUNCH(c, "fsm_scan_up", k_fsm_scan_up, ng, FSM_GROUP, c->d_summ, ntiles, gsum);
-        LAUNCH(c, "fsm_scan", k_fsm_scan, 1, 1024, (const uint4 *)gsum, ng, c->d_entry, c->d_meta, aux.s_init);
+        return DC_OK;
     }
-    if (write) {
-        const uint64_t wgrid = ntiles ? ntiles : 1;
-        if constexpr (SmMode<M>::fast)
-            LAUNCH(c, SmMode<M>::dec ? "small_dec_write" : "small_write", k_small_write<M>, wgrid, SmMode<M>::wthreads, d_in, len, nelem, (const uint64_t *)c->d_entry,
-                   (const uint4 *)c->d_summ, (const uint64_t *)c->d_meta, d_out);
-        else if (M == M_NYB_ENC && !aux.rk && ntiles && !((uintptr_t)d_in & 15) && !c->opt_nyb_wtile_off)
-            LAUNCH(c, FsmMode<M>::wname, k_nyb_enc_wtile<false>, (ntiles + 3) / 4, 256, d_in, len, nelem, ntiles,
-                   (const uint64_t *)c->d_entry, (const uint4 *)c->d_summ, (const uint64_t *)c->d_meta, d_out, aux);
-        else if (M == M_NYB_ENC && aux.rk && ntiles && !((uintptr_t)d_in & 15) && !((uintptr_t)aux.rk & 15) &&
-                 !c->opt_nyb_wtile_off)
-            LAUNCH(c, FsmMode<M>::wname, k_nyb_enc_wtile<true>, (ntiles + 3) / 4, 256, d_in, len, nelem, ntiles,
-                   (const uint64_t *)c->d_entry, (const uint4 *)c->d_summ, (const uint64_t *)c->d_meta, d_out, aux);
-        else if (M == M_NYB_DEC && ntiles && !((uintptr_t)d_in & 15) && !c->opt_nyb_wtile_off)
-            LAUNCH(c, FsmMode<M>::wname, k_nyb_dec_wtile, (ntiles + 3) / 4, 256, d_in, len, nelem, ntiles,
-                   (const uint64_t *)c->d_entry, (const uint4 *)c->d_summ, d_out, aux);
-        else
-            LAUNCH(c, FsmMode<M>::wname, k_fsm_write<M>, wgrid, 256, d_in, len, nelem, (const uint64_t *)c->d_entry,
-                   (const uint4 *)c->d_summ, (const uint64_t *)c->d_meta, d_out, aux);
+    if (M == M_SMALL_DEC && summ.gexp)
+        LAUNCH(c, "small_dec_summ", k_small_dec_summ, (ntiles + 255) / 256, 256, summ.gexp, summ.ngroups, d_in, len, ntiles,
+               c->ws.summ.get(), c->d_meta);
+    else if constexpr (SmMode<M>::fast) LAUNCH(c, name, k_small_tiles<M>, ntiles, 256, d_in, len, nelem, c->ws.summ.get());
+    else if (M == M_NYB_ENC && aux.frec && !summ.resolved) return DC_E_STATE;   // (ranks with unsettled first touches)
+    else if (summ.resolved) {   // (k_mtf_resolve's: the scan below rewrites ws.summ in place)
+        if (!c->summ_fresh)
+            HIPCHK(hipMemcpyAsync(c->ws.summ, c->ws.fraw, ntiles * sizeof(uint4), hipMemcpyDeviceToDevice, c->stream));
     }
-    HIPCHK(hipMemcpyAsync(c->h_pinned, c->d_meta, 9 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (gexp && c->h_pinned[8] != 8) return DC_E_STREAM;   // (dc_small_huff_decode: not a type-8 stream)
-    if (h_plan) for (int k = 0; k < 4; ++k) h_plan[k] = c->h_pinned[2 + k];
-    c->fsm_in = write ? nullptr : d_in; c->fsm_len = len; c->fsm_nelem = nelem; c->fsm_mode = M;
+    else if ((M == M_NYB_ENC && !aux.rk) || M == M_NYB_DEC || M == M_NYB_DBODY)
+        LAUNCH(c, name, k_nyb_tiles<M == M_NYB_DEC ? M_NYB_DEC : M == M_NYB_DBODY ? M_NYB_DBODY : M_NYB_ENC>,
+               (ntiles + 4 * NYB_TPW - 1) / (4 * NYB_TPW), 256, d_in, len, nelem, ntiles, c->ws.summ.get());
+    else LAUNCH(c, name, k_fsm_tiles<M>, ntiles, 256, d_in, len, nelem, c->ws.summ.get(), aux);
+    c->summ_fresh = false;   // (ws.summ rewritten in place: no longer the resolver's summaries)
+    LAUNCH(c, "fsm_scan_up", k_fsm_scan_up, ng, FSM_GROUP, c->ws.summ.get(), ntiles, gsum);
+    LAUNCH(c, "fsm_scan", k_fsm_scan, 1, 1024, (const uint4 *)gsum, ng, c->ws.entry.get(), c->d_meta, aux.s_init);
+    return DC_OK;
+}
+
+// The write launch. The nybble modes write with the wave-per-tile kernels when there are tiles, the input (and
+// the ranks) are 16-B aligned and DC_OPT_NYB_WTILE_OFF is not set; with k_fsm_write otherwise.
+template <int M>
+static int fsm_write(dc_ctx *c, const uint8_t *d_in, uint64_t len, uint64_t nelem, uint8_t *d_out, const FsmAux &aux)
+{
+    const uint64_t ntiles = fsm_ntiles<M>(d_in, nelem), wgrid = ntiles ? ntiles : 1;
+    const uint64_t *const entry = c->ws.entry, *const meta = c->d_meta;
+    const uint4 *const summ = c->ws.summ;
+    const bool wtile = ntiles && !((uintptr_t)d_in & 15) && !c->opt_nyb_wtile_off;
+    if constexpr (SmMode<M>::fast)
+        LAUNCH(c, SmMode<M>::dec ? "small_dec_write" : "small_write", k_small_write<M>, wgrid, SmMode<M>::wthreads, d_in, len,
+               nelem, entry, summ, meta, d_out);
+    else if (M == M_NYB_ENC && !aux.rk && wtile)
+        LAUNCH(c, FsmMode<M>::wname, k_nyb_enc_wtile<false>, (ntiles + 3) / 4, 256, d_in, len, nelem, ntiles, entry, summ, meta,
+               d_out, aux);
+    else if (M == M_NYB_ENC && aux.rk && wtile && !((uintptr_t)aux.rk & 15))
+        LAUNCH(c, FsmMode<M>::wname, k_nyb_enc_wtile<true>, (ntiles + 3) / 4, 256, d_in, len, nelem, ntiles, entry, summ, meta,
+               d_out, aux);
+    else if (M == M_NYB_DEC && wtile)
+        LAUNCH(c, FsmMode<M>::wname, k_nyb_dec_wtile, (ntiles + 3) / 4, 256, d_in, len, nelem, ntiles, entry, summ, d_out, aux);
+    else
+        LAUNCH(c, FsmMode<M>::wname, k_fsm_write<M>, wgrid, 256, d_in, len, nelem, entry, summ, meta, d_out, aux);
+    return DC_OK;
+}
+
+// the read-back of a run, and the length of what it writes (or, planned, would write)
+template <int M> static int fsm_finish(dc_ctx *c, uint64_t len, const FsmAux &aux, bool counted, FsmResult *res)
+{
+    uint64_t v[9];
+    if (const int r = read_back(c, c->d_meta, v, 9)) return r;
+    if (counted && v[8] != 8) return DC_E_STREAM;   // (dc_small_huff_decode: not a type-8 stream)
+    *res = FsmResult{v[0], v[1], {v[2], v[3], v[4], v[5]}, v[8], 0};
     const bool nyb = M == M_NYB_ENC;
     const bool enc = FsmMode<M>::enc || (nyb && aux.whole);
-    const uint64_t body = nyb ? c->h_pinned[0] + (aux.is_last ? c->h_pinned[1] : 0) : c->h_pinned[0];
-    uint64_t total = (FsmMode<M>::body || (nyb && !aux.whole)) ? body : enc ? 2 + body : 1 + body;
-    if (enc && total >= len) total = len + 1;
-    if (h_len) *h_len = total;
+    const uint64_t body = nyb ? res->count + (aux.is_last ? res->state : 0) : res->count;
+    res->total = (FsmMode<M>::body || (nyb && !aux.whole)) ? body : enc ? 2 + body : 1 + body;
+    if (enc && res->total >= len) res->total = len + 1;
     return DC_OK;
 }
 
-// the write pass alone, on the tile summaries and entries the last fsm_run(write = false) of
-// the same input left in the context (a shard body sized before its output is placed)
+// Count, scan, write into d_out and finish. With PLAN_ONLY for d_out nothing is written: *res is
+// what a write would give, and the summaries and entries stay for fsm_write_planned of this input.
+static uint8_t *const PLAN_ONLY = nullptr;
 template <int M>
-static int fsm_write_planned(dc_ctx *c, const uint8_t *d_in, uint64_t len, uint64_t nelem, uint8_t *d_out,
-                             uint64_t *h_len, FsmAux aux = FsmAux{nullptr, 0, 0, 1, 1})
+static int fsm_run(dc_ctx *c, const uint8_t *d_in, uint64_t len, uint64_t nelem, uint8_t *d_out, const char *name,
+                   const FsmAux &aux, const FsmSumm &summ, FsmResult *res)
 {
-    if (c->fsm_in != d_in || c->fsm_len != len || c->fsm_nelem != nelem || c->fsm_mode != M) return DC_E_STATE;
-    const uint64_t ntiles = SmMode<M>::fast ? sm_ntiles<M>(d_in, FsmOff<M>::v, nelem) : (nelem + FSM_TILE - 1) / FSM_TILE;
-    if constexpr (SmMode<M>::fast)
-        LAUNCH(c, SmMode<M>::dec ? "small_dec_write" : "small_write", k_small_write<M>, ntiles ? ntiles : 1, SmMode<M>::wthreads, d_in, len, nelem,
-               (const uint64_t *)c->d_entry, (const uint4 *)c->d_summ, (const uint64_t *)c->d_meta, d_out);
-    else if (M == M_NYB_ENC && !aux.rk && ntiles && !((uintptr_t)d_in & 15) && !c->opt_nyb_wtile_off)
-        LAUNCH(c, FsmMode<M>::wname, k_nyb_enc_wtile<false>, (ntiles + 3) / 4, 256, d_in, len, nelem, ntiles,
-               (const uint64_t *)c->d_entry, (const uint4 *)c->d_summ, (const uint64_t *)c->d_meta, d_out, aux);
-    else
-        LAUNCH(c, FsmMode<M>::wname, k_fsm_write<M>, ntiles ? ntiles : 1, 256, d_in, len, nelem, (const uint64_t *)c->d_entry,
-               (const uint4 *)c->d_summ, (const uint64_t *)c->d_meta, d_out, aux);
-    HIPCHK(hipMemcpyAsync(c->h_pinned, c->d_meta, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    c->fsm_in = nullptr;
-    if (h_len) *h_len = c->h_pinned[0];
+    if (const int r = fsm_count<M>(c, d_in, len, nelem, name, aux, summ)) return r;
+    if (d_out != PLAN_ONLY)
+        if (const int r = fsm_write<M>(c, d_in, len, nelem, d_out, aux)) return r;
+    if (const int r = fsm_finish<M>(c, len, aux, summ.gexp != nullptr, res)) return r;
+    c->fsm_in = d_out != PLAN_ONLY ? nullptr : d_in; c->fsm_len = len; c->fsm_nelem = nelem; c->fsm_mode = M;
+    return DC_OK;
+}
+// ... for the calls that want the length alone, into *h_len (the shard bodies: and the exit state)
+template <int M>
+static int fsm_stream(dc_ctx *c, const uint8_t *d_in, uint64_t len, uint64_t nelem, uint8_t *d_out, uint64_t *h_len,
+                      const char *name, const FsmAux &aux = aux_whole(), const FsmSumm &summ = summ_counted(),
+                      int *h_state_out = nullptr)
+{
+    FsmResult res;
+    if (const int r = fsm_run<M>(c, d_in, len, nelem, d_out, name, aux, summ, &res)) return r;
+    *h_len = res.total;
+    if (h_state_out) *h_state_out = (int)res.state;
     return DC_OK;
 }
 
-// the per-tile record counts of the last mtf_run(ranks)
-static const uint2 *mtf_heads(const dc_ctx *c, uint64_t)
+// the write pass alone, on the tile summaries and entries the last PLAN_ONLY run of the same input
+// left in the context (a shard body sized before its output is placed)
+template <int M>
+static int fsm_write_planned(dc_ctx *c, const uint8_t *d_in, uint64_t len, uint64_t nelem, uint8_t *d_out, uint64_t *h_len)
 {
-    return c->d_mhead;
+    static_assert(M == M_SMALL_BODY0 || M == M_SMALL_BODY1, "the small front-end bodies (dc_small_compress_body_write)");
+    if (c->fsm_in != d_in || c->fsm_len != len || c->fsm_nelem != nelem || c->fsm_mode != M) return DC_E_STATE;
+    if (const int r = fsm_write<M>(c, d_in, len, nelem, d_out, aux_whole())) return r;
+    if (const int r = read_back(c, c->d_meta, h_len)) return r;
+    c->fsm_in = nullptr;
+    return DC_OK;
 }
 
-// Adaptive nybble ranks (k_mtf_* pipeline) of elements 1..len-1 of d_in into c->d_rk, from the
+// Adaptive nybble ranks (k_mtf_* pipeline) of elements 1..len-1 of d_in into c->ws.rk, from the
 // entry lists h_init. ranks = false: only the composition of the whole input from h_init
 // into *h_final (a shard summary when h_init is empty).
 static int mtf_run(dc_ctx *c, const uint8_t *d_in, uint64_t len, const MtfSum *h_init, bool ranks, MtfSum *h_final)
@@ -7804,27 +7837,27 @@ static int mtf_run(dc_ctx *c, const uint8_t *d_in, uint64_t len, const MtfSum *h
         if (n <= MTF_FAN) break;
     }
     // layout: [summaries, all levels][entries, all levels][init][final]
-    if (ensure((void **)&c->d_mtf, &c->mtf_cap, (2 * tot + 2) * sizeof(MtfSum))) return DC_E_HIP;
-    MtfSum *S = c->d_mtf, *E = c->d_mtf + tot, *init = c->d_mtf + 2 * tot, *fin = init + 1;
+    if (ensure(c->ws.mtf, (2 * tot + 2) * sizeof(MtfSum))) return DC_E_HIP;
+    MtfSum *S = c->ws.mtf, *E = c->ws.mtf + tot, *init = c->ws.mtf + 2 * tot, *fin = init + 1;
     // the entry lists through a pinned copy: no wait here (the stream is idle at every call: the
     // calls that follow an mtf_run end by reading back on it)
     if (!c->h_mtf && hipHostMalloc((void **)&c->h_mtf, sizeof(MtfSum), 0) != hipSuccess) return DC_E_HIP;
     memcpy(c->h_mtf, h_init, sizeof(MtfSum));
     HIPCHK(hipMemcpyAsync(init, c->h_mtf, sizeof(MtfSum), hipMemcpyHostToDevice, c->stream));
-    if (ranks && ensure((void **)&c->d_rk, &c->rk_cap, ((len + 3) & ~3ull))) return DC_E_HIP;
-    if (ranks && (ensure((void **)&c->d_mrec, &c->mrec_cap, n0 * 2 * MTF_REC * sizeof(uint4)) ||
-                  ensure((void **)&c->d_mhead, &c->mhead_cap, n0 * sizeof(uint2)) ||
-                  ensure((void **)&c->d_fraw, &c->fraw_cap, n0 * sizeof(uint4))))
+    if (ranks && ensure(c->ws.rk, ((len + 3) & ~3ull))) return DC_E_HIP;
+    if (ranks && (ensure(c->ws.mrec, n0 * 2 * MTF_REC * sizeof(uint4)) || ensure(c->ws.mhead, n0 * sizeof(uint2)) ||
+                  ensure(c->ws.fraw, n0 * sizeof(uint4))))
         return DC_E_HIP;
-    uint4 *const mrec = c->d_mrec;
-    uint2 *const mhead = c->d_mhead;
+    uint8_t *const rk = c->ws.rk;
+    uint4 *const mrec = c->ws.mrec;
+    uint2 *const mhead = c->ws.mhead;
     // a tile's elements start (1 + d_in % 16) % 16 bytes into its first granule: within its first
     // dword for the usual 16-B aligned input (k_mtf_walk<0/2>, no dword selects), anywhere (<1/3>)
     const bool gen = (((uintptr_t)d_in + 1) & 15u) >= 4u;
     if (ranks && !gen)   // the summaries, the ranks but for the first touches, and their list: one walk
-        LAUNCH(c, "mtf_tiles", k_mtf_walk<2>, (n0 + 255) / 256, 256, d_in, len, n0, S, c->d_rk, mrec, mhead);
+        LAUNCH(c, "mtf_tiles", k_mtf_walk<2>, (n0 + 255) / 256, 256, d_in, len, n0, S, rk, mrec, mhead);
     else if (ranks)
-        LAUNCH(c, "mtf_tiles", k_mtf_walk<3>, (n0 + 255) / 256, 256, d_in, len, n0, S, c->d_rk, mrec, mhead);
+        LAUNCH(c, "mtf_tiles", k_mtf_walk<3>, (n0 + 255) / 256, 256, d_in, len, n0, S, rk, mrec, mhead);
     else if (!gen)
         LAUNCH(c, "mtf_tiles", k_mtf_walk<0>, (n0 + 255) / 256, 256, d_in, len, n0, S, (uint8_t *)nullptr,
                (uint4 *)nullptr, (uint2 *)nullptr);
@@ -7840,17 +7873,14 @@ static int mtf_run(dc_ctx *c, const uint8_t *d_in, uint64_t len, const MtfSum *h
         LAUNCH(c, "mtf_down", k_mtf_down, (groups * 16 + 255) / 256, 256, (const MtfSum *)(S + off[l]), nl[l], pe,
                E + off[l], l == levels - 1 ? fin : (MtfSum *)nullptr);
     }
-    if (ranks) {   // and the nybble encoder's tile summaries (fsm_run(..., summ_ready)): its tiles are these
+    if (ranks) {   // and the nybble encoder's tile summaries (summ_resolved): its tiles are these
         const uint64_t ng = (n0 + FSM_GROUP - 1) / FSM_GROUP;
-        if (ensure((void **)&c->d_summ, &c->summ_cap, (n0 + ng) * sizeof(uint4))) return DC_E_HIP;
+        if (ensure(c->ws.summ, (n0 + ng) * sizeof(uint4))) return DC_E_HIP;
         LAUNCH(c, "mtf_ranks", k_mtf_resolve, (n0 + 255) / 256, 256, len, n0, (const MtfSum *)E, mrec,
-               (const uint2 *)mhead, c->d_rk, c->d_fraw, c->d_summ);
+               (const uint2 *)mhead, rk, c->ws.fraw.get(), c->ws.summ.get());
         c->summ_fresh = true;
     }
-    if (h_final) {
-        HIPCHK(hipMemcpyAsync(h_final, fin, sizeof(MtfSum), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-    }
+    if (h_final && dc_memcpy_d2h(c, h_final, fin, sizeof(MtfSum))) return DC_E_HIP;
     c->rk_in = ranks ? d_in : nullptr; c->rk_len = len;
     return DC_OK;
 }
@@ -7861,13 +7891,13 @@ static int mtf_run(dc_ctx *c, const uint8_t *d_in, uint64_t len, const MtfSum *h
 static int adec_fast(dc_ctx *c, uint8_t *d_out, uint64_t n)
 {
     const uint64_t seg = std::min<uint64_t>(n - 1, ADEC_SEG);
-    if (ensure((void **)&c->d_actl, &c->actl_cap, (seg + 64) * sizeof(uint32_t))) return DC_E_HIP;
+    if (ensure(c->ws.actl, (seg + 64) * sizeof(uint32_t))) return DC_E_HIP;
     if (!c->d_astate && hipMalloc(&c->d_astate, 64 * sizeof(uint32_t)) != hipSuccess) return DC_E_HIP;
     for (uint64_t k0 = 1; k0 < n; k0 += ADEC_SEG) {
         const uint64_t k1 = std::min<uint64_t>(k0 + ADEC_SEG, n);
         const uint64_t grid = std::min<uint64_t>((k1 - k0 + 255) / 256, 8192);
-        LAUNCH(c, "nyb_adec_ctl", k_nyb_adec_ctl, grid, 256, (const uint8_t *)d_out, k0, k1, n, c->d_actl);
-        LAUNCH(c, "nyb_resolve", k_nyb_resolve_c, 1, 64, d_out, k0, k1, (const uint32_t *)c->d_actl, c->d_astate,
+        LAUNCH(c, "nyb_adec_ctl", k_nyb_adec_ctl, grid, 256, (const uint8_t *)d_out, k0, k1, n, c->ws.actl.get());
+        LAUNCH(c, "nyb_resolve", k_nyb_resolve_c, 1, 64, d_out, k0, k1, (const uint32_t *)c->ws.actl, c->d_astate,
                k0 == 1 ? 1 : 0);
     }
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -7877,40 +7907,28 @@ static int adec_fast(dc_ctx *c, uint8_t *d_out, uint64_t n)
 static MtfSum mtf_initial()   // initialize_dictionary (nybble_compression.c:546-562)
 {
     MtfSum s;
-    uint64_t L = 0;
-    const char *init = " etaoins";
-    for (int k = 0; k < 8; ++k) L |= (uint64_t)(uint8_t)init[k] << (8 * k);
-    for (int q = 0; q < 16; ++q) { s.L[q] = L; s.cnt[q] = 8; }
+    for (int q = 0; q < 16; ++q) { s.L[q] = NYB_DICT; s.cnt[q] = 8; }   // entry k in byte k
     return s;
 }
 
-static int read_byte(dc_ctx *c, const uint8_t *d, uint8_t *v)
+// the stream of no bytes: a lone ' '
+static int empty_stream(dc_ctx *c, uint8_t *d_out, uint64_t *h_len)
 {
-    HIPCHK(hipMemcpyAsync(c->h_pinned, d, 1, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemsetAsync(d_out, ' ', 1, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    *v = *(uint8_t *)c->h_pinned;
+    *h_len = 1;
     return DC_OK;
 }
 
-static int write_byte(dc_ctx *c, uint8_t *d, uint8_t v)
+// decoder type dispatch shared by nybble and small (:744, :799, :806): 1 when the type byte was one
+// of these (the bytes copied, *h_len set), 0 when it is the caller's, or an error
+static int copy_typed(dc_ctx *c, const uint8_t *d_in, uint64_t m, uint8_t type, uint8_t *d_out, uint64_t *h_len)
 {
-    HIPCHK(hipMemsetAsync(d, v, 1, c->stream));
-    return DC_OK;
-}
-
-// decoder type dispatch shared by nybble and small (:744, :799, :806)
-static int copy_typed(dc_ctx *c, const uint8_t *d_in, uint64_t m, uint8_t type, uint8_t *d_out, uint64_t *h_len,
-                      bool *handled)
-{
-    *handled = true;
-    if (type == ' ') {
-        if (m > 1) HIPCHK(hipMemcpyAsync(d_out, d_in + 1, m - 1, hipMemcpyDeviceToDevice, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-        *h_len = m - 1;
-        return DC_OK;
-    }
-    *handled = false;
-    return DC_OK;
+    if (type != ' ') return 0;
+    if (m > 1) HIPCHK(hipMemcpyAsync(d_out, d_in + 1, m - 1, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    *h_len = m - 1;
+    return 1;
 }
 
 extern "C" {
@@ -7918,18 +7936,30 @@ extern "C" {
 int dc_nyb_compress(dc_ctx *c, const uint8_t *d_in, uint64_t n, int modify, uint8_t *d_out, uint64_t *h_len)
 {
     if (!c || !d_out || !h_len || (n && !d_in)) return DC_E_ARG;
-    if (n == 0) { int r = write_byte(c, d_out, ' '); if (r) return r; HIPCHK(hipStreamSynchronize(c->stream)); *h_len = 1; return DC_OK; }
-    if (!modify) return fsm_run<M_NYB_ENC>(c, d_in, n, n - 1, d_out, h_len, "nyb_enc_tiles");
+    if (n == 0) return empty_stream(c, d_out, h_len);
+    if (!modify) return fsm_stream<M_NYB_ENC>(c, d_in, n, n - 1, d_out, h_len, "nyb_enc_tiles");
     const MtfSum init = mtf_initial();
-    int r = mtf_run(c, d_in, n, &init, true, nullptr);
-    if (r) return r;
-    // (the tile summaries: k_mtf_resolve's, when there are ranks)
-    return fsm_run<M_NYB_ENC>(c, d_in, n, n - 1, d_out, h_len, "nyb_enca_tiles",
-                              FsmAux{n > 1 ? c->d_rk : nullptr, 0, 0, 1, 1, 0, c->d_mrec, mtf_heads(c, n)}, nullptr, true,
-                              nullptr, 0, n > 1);
+    if (const int r = mtf_run(c, d_in, n, &init, true, nullptr)) return r;
+    return fsm_stream<M_NYB_ENC>(c, d_in, n, n - 1, d_out, h_len, "nyb_enca_tiles", aux_adaptive(c, aux_whole(), n > 1),
+                                 summ_resolved(n > 1));
 }
 
 // ---- chunked nybble container (DCNK) ---------------------------------------------------
+struct NybkHead {   // the container's first NYBK_HEAD bytes
+    uint32_t magic, version, modify, K;
+    uint64_t n, nch;
+};
+static_assert(sizeof(NybkHead) == NYBK_HEAD, "DCNK header");
+
+// the header of a container, read and checked: what dc_nyb_chunked_info and the decode begin with
+static int nybk_head(dc_ctx *c, const uint8_t *d_in, uint64_t m, NybkHead *h)
+{
+    if (!c || !d_in || m < NYBK_HEAD) return DC_E_ARG;
+    if (const int r = read_back(c, d_in, h)) return r;
+    if (h->magic != NYBK_MAGIC || h->version != 1 || h->K < 16) return DC_E_STREAM;
+    return DC_OK;
+}
+
 uint64_t dc_nyb_chunked_bound(uint64_t n, uint32_t K)
 {
     const uint64_t nch = (n && K) ? (n + K - 1) / K : 0;
@@ -7943,10 +7973,8 @@ int dc_nyb_compress_chunked(dc_ctx *c, const uint8_t *d_in, uint64_t n, int modi
     const uint64_t nch = n ? (n + K - 1) / K : 0;
     const uint64_t head = NYBK_HEAD + 8 * (nch + 1);
     if (out_cap < head) return DC_E_CAPACITY;
-    uint32_t *h = (uint32_t *)c->h_pinned;
-    h[0] = NYBK_MAGIC; h[1] = 1; h[2] = modify ? 1 : 0; h[3] = K;
-    c->h_pinned[2] = n; c->h_pinned[3] = nch;
-    HIPCHK(hipMemcpyAsync(d_out, c->h_pinned, NYBK_HEAD, hipMemcpyHostToDevice, c->stream));
+    const NybkHead h{NYBK_MAGIC, 1, modify ? 1u : 0u, K, n, nch};
+    if (const int r = upload(c, d_out, &h, sizeof(h))) return r;
     uint64_t *off = (uint64_t *)(d_out + NYBK_HEAD);
     if (nch == 0) {
         HIPCHK(hipMemsetAsync(off, 0, 8, c->stream));
@@ -7954,16 +7982,15 @@ int dc_nyb_compress_chunked(dc_ctx *c, const uint8_t *d_in, uint64_t n, int modi
         *h_len = head;
         return DC_OK;
     }
-    if (ensure((void **)&c->d_kscr, &c->kscr_cap, nch * ((uint64_t)K + 2))) return DC_E_HIP;
-    if (ensure((void **)&c->d_klens, &c->klens_cap, nch * sizeof(uint64_t))) return DC_E_HIP;
-    LAUNCH(c, "nyb_chunk_enc", k_nyb_chunk_enc, (nch + 63) / 64, 64, d_in, n, K, nch, modify ? 1 : 0, c->d_kscr,
-           c->d_klens);
-    LAUNCH(c, "nyb_chunk_scan", k_scan_u64, 1, 1024, (const uint64_t *)c->d_klens, nch, off);
-    HIPCHK(hipMemcpyAsync(c->h_pinned, off + nch, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    const uint64_t total = c->h_pinned[0];
+    if (ensure(c->ws.kscr, nch * ((uint64_t)K + 2))) return DC_E_HIP;
+    if (ensure(c->ws.klens, nch * sizeof(uint64_t))) return DC_E_HIP;
+    LAUNCH(c, "nyb_chunk_enc", k_nyb_chunk_enc, (nch + 63) / 64, 64, d_in, n, K, nch, modify ? 1 : 0, c->ws.kscr.get(),
+           c->ws.klens.get());
+    LAUNCH(c, "nyb_chunk_scan", k_scan_u64, 1, 1024, (const uint64_t *)c->ws.klens, nch, off);
+    uint64_t total = 0;
+    if (const int r = read_back(c, off + nch, &total)) return r;
     if (out_cap < head + total) return DC_E_CAPACITY;
-    LAUNCH(c, "nyb_chunk_copy", k_nyb_chunk_copy, nch, 256, (const uint8_t *)c->d_kscr, K, (const uint64_t *)off,
+    LAUNCH(c, "nyb_chunk_copy", k_nyb_chunk_copy, nch, 256, (const uint8_t *)c->ws.kscr, K, (const uint64_t *)off,
            d_out + head);
     HIPCHK(hipStreamSynchronize(c->stream));
     *h_len = head + total;
@@ -7972,14 +7999,11 @@ int dc_nyb_compress_chunked(dc_ctx *c, const uint8_t *d_in, uint64_t n, int modi
 
 int dc_nyb_chunked_info(dc_ctx *c, const uint8_t *d_in, uint64_t m, uint64_t *h_n, int *h_modify, uint32_t *h_K)
 {
-    if (!c || !d_in || m < NYBK_HEAD) return DC_E_ARG;
-    HIPCHK(hipMemcpyAsync(c->h_pinned, d_in, NYBK_HEAD, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    const uint32_t *h = (const uint32_t *)c->h_pinned;
-    if (h[0] != NYBK_MAGIC || h[1] != 1 || h[3] < 16) return DC_E_STREAM;
-    if (h_n) *h_n = c->h_pinned[2];
-    if (h_modify) *h_modify = (int)h[2];
-    if (h_K) *h_K = h[3];
+    NybkHead h;
+    if (const int r = nybk_head(c, d_in, m, &h)) return r;
+    if (h_n) *h_n = h.n;
+    if (h_modify) *h_modify = (int)h.modify;
+    if (h_K) *h_K = h.K;
     return DC_OK;
 }
 
@@ -7987,12 +8011,11 @@ int dc_nyb_decompress_chunked(dc_ctx *c, const uint8_t *d_in, uint64_t m, uint8_
                               uint64_t *h_len)
 {
     if (!c || !d_out || !h_len || !d_in || ((uintptr_t)d_in & 7)) return DC_E_ARG;
-    uint64_t n = 0;
-    int modify = 0;
-    uint32_t K = 0;
-    int r = dc_nyb_chunked_info(c, d_in, m, &n, &modify, &K);
-    if (r) return r;
-    const uint64_t nch = c->h_pinned[3];
+    NybkHead h;
+    if (const int r = nybk_head(c, d_in, m, &h)) return r;
+    const uint64_t n = h.n, nch = h.nch;
+    const uint32_t K = h.K;
+    const int modify = (int)h.modify;
     if (nch != (n ? (n + K - 1) / K : 0) || m < NYBK_HEAD + 8 * (nch + 1)) return DC_E_STREAM;
     if (out_cap < n) return DC_E_CAPACITY;
     *h_len = n;
@@ -8002,9 +8025,9 @@ int dc_nyb_decompress_chunked(dc_ctx *c, const uint8_t *d_in, uint64_t m, uint8_
     HIPCHK(hipMemsetAsync(err, 0, 8, c->stream));
     LAUNCH(c, "nyb_chunk_dec", k_nyb_chunk_dec, (nch + 63) / 64, 64, d_in + head,
            (const uint64_t *)(d_in + NYBK_HEAD), m - head, n, K, nch, modify, d_out, err);
-    HIPCHK(hipMemcpyAsync(c->h_pinned, err, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return c->h_pinned[0] ? DC_E_STREAM : DC_OK;
+    uint64_t bad = 0;
+    if (const int r = read_back(c, err, &bad)) return r;
+    return bad ? DC_E_STREAM : DC_OK;
 }
 
 int dc_nyb_decompress_batch(dc_ctx *c, const uint8_t *d_in, const uint64_t *d_in_off, uint64_t count, int modify,
@@ -8017,28 +8040,25 @@ int dc_nyb_decompress_batch(dc_ctx *c, const uint8_t *d_in, const uint64_t *d_in
         HIPCHK(hipStreamSynchronize(c->stream));
         return DC_OK;
     }
-    if (ensure((void **)&c->d_klens, &c->klens_cap, count * sizeof(uint64_t))) return DC_E_HIP;
+    if (ensure(c->ws.klens, count * sizeof(uint64_t))) return DC_E_HIP;
     uint64_t *err = c->d_meta + 8;
     HIPCHK(hipMemsetAsync(err, 0, 8, c->stream));
     const uint64_t grid = (count + 63) / 64;
-    LAUNCH(c, "nyb_batch_len", k_nyb_batch_len, grid, 64, d_in, d_in_off, count, c->d_klens, err);
-    LAUNCH(c, "nyb_batch_scan", k_scan_u64, 1, 1024, (const uint64_t *)c->d_klens, count, d_out_off);
-    HIPCHK(hipMemcpyAsync(c->h_pinned, d_out_off + count, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(c->h_pinned + 1, err, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    const uint64_t total = c->h_pinned[0];
-    if (c->h_pinned[1]) return DC_E_ARG;
+    LAUNCH(c, "nyb_batch_len", k_nyb_batch_len, grid, 64, d_in, d_in_off, count, c->ws.klens.get(), err);
+    LAUNCH(c, "nyb_batch_scan", k_scan_u64, 1, 1024, (const uint64_t *)c->ws.klens, count, d_out_off);
+    uint64_t total = 0, bad = 0;
+    if (const int r = read_back2(c, d_out_off + count, &total, err, &bad)) return r;
+    if (bad) return DC_E_ARG;
     *h_total = total;
     if (total > out_cap || (total && !d_out)) return DC_E_CAPACITY;
     LAUNCH(c, "nyb_batch_dec", k_nyb_batch_dec, grid, 64, d_in, d_in_off, (const uint64_t *)d_out_off, count, modify,
            d_out, err);
-    HIPCHK(hipMemcpyAsync(c->h_pinned, err, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return c->h_pinned[0] ? DC_E_STREAM : DC_OK;
+    if (const int r = read_back(c, err, &bad)) return r;
+    return bad ? DC_E_STREAM : DC_OK;
 }
 
 // ---- byte-stream batch v1 (dc_gpu.h): what the four nybble and small batch calls begin with ----
-// 1 (nothing to do), 0 with d_hb sized for `count` lengths and the first-failure slot turned over,
+// 1 (nothing to do), 0 with ws.hb sized for `count` lengths and the first-failure slot turned over,
 // or an error.
 static int sbatch_begin(dc_ctx *c, const uint8_t *d_in, const uint64_t *d_in_off, uint64_t count, const uint8_t *d_out,
                         const uint64_t *d_out_off, const int32_t *d_status, unsigned long long **first)
@@ -8057,7 +8077,7 @@ int dc_nyb_compress_batch(dc_ctx *c, const uint8_t *d_in, const uint64_t *d_in_o
 {
     unsigned long long *first;
     if (const int r = sbatch_begin(c, d_in, d_in_off, count, d_out, d_out_off, d_status, &first)) return r > 0 ? DC_OK : r;
-    uint64_t *const lens = c->d_hb + 2;
+    uint64_t *const lens = c->ws.hb + 2;
     const uint64_t grid = (count + 63) / 64;
     LAUNCH(c, "nyb_batch_enc_len", k_nyb_batch_enc_len, grid, 64, d_in, d_in_off, count, modify ? 1 : 0, lens);
     LAUNCH(c, "nyb_batch_enc_scan", k_scan_u64, 1, 1024, (const uint64_t *)lens, count, d_out_off);
@@ -8084,7 +8104,7 @@ int dc_small_compress_batch(dc_ctx *c, const uint8_t *d_in, const uint64_t *d_in
 {
     unsigned long long *first;
     if (const int r = sbatch_begin(c, d_in, d_in_off, count, d_out, d_out_off, d_status, &first)) return r > 0 ? DC_OK : r;
-    uint64_t *const lens = c->d_hb + 2;
+    uint64_t *const lens = c->ws.hb + 2;
     const uint64_t grid = hbatch_grid(c, (count + SB_WAVES - 1) / SB_WAVES, 2048);   // a wave per buffer, 8 workgroups per CU
     LAUNCH(c, "small_batch_len", k_small_batch_len, grid, SB_THREADS, d_in, d_in_off, count, lens);
     LAUNCH(c, "small_batch_scan", k_scan_u64, 1, 1024, (const uint64_t *)lens, count, d_out_off);
@@ -8122,10 +8142,10 @@ int dc_crc32(dc_ctx *c, const uint8_t *d_in, uint64_t n, uint32_t *d_crc)
         return DC_OK;
     }
     const uint64_t np = (n - 1) / DC_CRC_PIECE + 1;
-    if (ensure((void **)&c->d_crcp, &c->crcp_cap, np * sizeof(uint32_t))) return DC_E_HIP;
+    if (ensure(c->ws.crcp, np * sizeof(uint32_t))) return DC_E_HIP;
     const uint64_t grid = hbatch_grid(c, (np + CRC_WAVES - 1) / CRC_WAVES, 2048);   // a wave per piece, 8 workgroups per CU
-    LAUNCH(c, "crc_pieces", k_crc_pieces, grid, CRC_THREADS, d_in, n, np, c->d_crcp, (const uint32_t *)c->d_crct);
-    LAUNCH(c, "crc_fold", k_crc_fold, 1, 1024, (const uint32_t *)c->d_crcp, np, d_crc);
+    LAUNCH(c, "crc_pieces", k_crc_pieces, grid, CRC_THREADS, d_in, n, np, c->ws.crcp, (const uint32_t *)c->d_crct);
+    LAUNCH(c, "crc_fold", k_crc_fold, 1, 1024, (const uint32_t *)c->ws.crcp, np, d_crc);
     return DC_OK;
 }
 
@@ -8168,50 +8188,38 @@ int dc_nyb_mtf_summary(dc_ctx *c, const uint8_t *d_in, uint64_t len, uint8_t *h_
     if (!c || !h_lists || !h_cnt || (len && !d_in)) return DC_E_ARG;
     MtfSum empty, fin;
     memset(&empty, 0, sizeof(empty));
-    int r = mtf_run(c, d_in, len, &empty, false, &fin);
-    if (r) return r;
+    if (const int r = mtf_run(c, d_in, len, &empty, false, &fin)) return r;
     memcpy(h_lists, fin.L, 128);
     memcpy(h_cnt, fin.cnt, 16);
     return DC_OK;
 }
 
-static int lists_in(const uint8_t *h_lists, MtfSum *s)
+static void lists_in(const uint8_t *h_lists, MtfSum *s)
 {
     memcpy(s->L, h_lists, 128);
     for (int q = 0; q < 16; ++q) s->cnt[q] = 8;
-    return DC_OK;
 }
 
 int dc_nyb_body_plan(dc_ctx *c, const uint8_t *d_in, uint64_t len, int modify, const uint8_t *h_lists,
                      uint64_t *h_plan)
 {
     if (!c || !h_plan || !d_in || len < 1 || (modify && !h_lists)) return DC_E_ARG;
-    FsmAux aux{nullptr, 0, 0, 0, 0};
+    FsmAux aux = aux_body(-1, false);
     if (modify) {
         MtfSum init;
         lists_in(h_lists, &init);
-        int r = mtf_run(c, d_in, len, &init, true, nullptr);
-        if (r) return r;
-        aux.rk = len > 1 ? c->d_rk : nullptr;
-        aux.frec = c->d_mrec;
-        aux.fhead = mtf_heads(c, len);
+        if (const int r = mtf_run(c, d_in, len, &init, true, nullptr)) return r;
+        aux = aux_adaptive(c, aux, len > 1);
     }
-    int r = fsm_run<M_NYB_ENC>(c, d_in, len, len - 1, nullptr, nullptr, "nyb_body_tiles", aux, h_plan, false,
-                               nullptr, 0, modify && len > 1);
+    FsmResult res;
+    int r = fsm_run<M_NYB_ENC>(c, d_in, len, len - 1, PLAN_ONLY, "nyb_body_tiles", aux, summ_resolved(modify && len > 1), &res);
     if (r) return r;
+    for (int k = 0; k < 4; ++k) h_plan[k] = res.comp[k];
     // rank of the last element (the byte a pending nybble of this shard belongs to)
     uint8_t last = 0xFF;
     if (len > 1) {
-        if (modify) HIPCHK(hipMemcpyAsync(c->h_pinned, c->d_rk + (len - 2), 1, hipMemcpyDeviceToHost, c->stream));
-        else HIPCHK(hipMemcpyAsync(c->h_pinned, d_in + (len - 1), 1, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-        last = *(uint8_t *)c->h_pinned;
-        if (!modify) {
-            const char *t = " etaoins";
-            const uint8_t b = last;
-            last = 0xFF;
-            for (int k = 0; k < 8; ++k) if ((uint8_t)t[k] == b) { last = (uint8_t)k; break; }
-        }
+        if (read_back(c, modify ? c->ws.rk + (len - 2) : d_in + (len - 1), &last)) return DC_E_HIP;
+        if (!modify) last = dict_rank(last);
     }
     h_plan[4] = last;
     return DC_OK;
@@ -8222,39 +8230,33 @@ int dc_nyb_body_write(dc_ctx *c, const uint8_t *d_in, uint64_t len, int modify, 
 {
     if (!c || !d_out || !h_len || !d_in || len < 1 || pend_rank > 7) return DC_E_ARG;
     if (modify && len > 1 && (c->rk_in != d_in || c->rk_len != len)) return DC_E_ARG;   // plan this input first
-    // the first-touch records only with ranks (an earlier adaptive call leaves d_mrec set: a
-    // static body passing it would trip fsm_run's unsettled-ranks guard)
+    // the first-touch records only with ranks (an earlier adaptive call leaves ws.mrec set: a
+    // static body passing it would trip fsm_count's unsettled-ranks guard)
     const bool adaptive = modify && len > 1;
-    FsmAux aux{adaptive ? c->d_rk : nullptr, pend_rank < 0 ? 0u : (uint32_t)pend_rank,
-               pend_rank < 0 ? 0u : 1u, is_last ? 1u : 0u, 0, 0, adaptive ? c->d_mrec : nullptr,
-               adaptive ? mtf_heads(c, len) : nullptr};
+    const FsmAux body = aux_body(pend_rank, is_last != 0), aux = adaptive ? aux_adaptive(c, body, true) : body;
     // a shard of no elements that ends the stream while a nybble is pending: the odd-tail byte is
     // the pending byte itself, d_in[0] (the writers' odd tail is an element of the shard, len >= 2)
     if (len == 1 && is_last && pend_rank >= 0)
         HIPCHK(hipMemcpyAsync(d_out, d_in, 1, hipMemcpyDeviceToDevice, c->stream));
-    int r = fsm_run<M_NYB_ENC>(c, d_in, len, len - 1, d_out, h_len, "nyb_body_tiles", aux, nullptr, true, nullptr,
-                               0, modify && len > 1);
-    if (r) return r;
-    if (h_state_out) *h_state_out = (int)c->h_pinned[1];
-    return DC_OK;
+    return fsm_stream<M_NYB_ENC>(c, d_in, len, len - 1, d_out, h_len, "nyb_body_tiles", aux, summ_resolved(adaptive), h_state_out);
 }
 
 int dc_nyb_dbody_plan(dc_ctx *c, const uint8_t *d_in, uint64_t len, uint64_t m, uint64_t *h_plan)
 {
     if (!c || !h_plan || (m && !d_in) || m > len || len > m + 1) return DC_E_ARG;
-    return fsm_run<M_NYB_DBODY>(c, d_in, len, m, nullptr, nullptr, "nyb_dbody_tiles", FsmAux{nullptr, 0, 0, 0, 0},
-                                h_plan, false);
+    FsmResult res;
+    if (const int r = fsm_run<M_NYB_DBODY>(c, d_in, len, m, PLAN_ONLY, "nyb_dbody_tiles", aux_dbody(0), summ_counted(), &res))
+        return r;
+    for (int k = 0; k < 4; ++k) h_plan[k] = res.comp[k];
+    return DC_OK;
 }
 
 int dc_nyb_dbody_write(dc_ctx *c, const uint8_t *d_in, uint64_t len, uint64_t m, int s_in, uint8_t *d_out,
                        uint64_t *h_len, int *h_state_out)
 {
     if (!c || !d_out || !h_len || (m && !d_in) || m > len || len > m + 1 || (s_in & ~1)) return DC_E_ARG;
-    int r = fsm_run<M_NYB_DBODY>(c, d_in, len, m, d_out, h_len, "nyb_dbody_tiles",
-                                 FsmAux{nullptr, 0, (uint32_t)s_in, 0, 0});
-    if (r) return r;
-    if (h_state_out) *h_state_out = (int)c->h_pinned[1];
-    return DC_OK;
+    return fsm_stream<M_NYB_DBODY>(c, d_in, len, m, d_out, h_len, "nyb_dbody_tiles", aux_dbody((uint32_t)s_in), summ_counted(),
+                                   h_state_out);
 }
 
 int dc_nyb_decompress(dc_ctx *c, const uint8_t *d_in, uint64_t m, int modify, uint8_t *d_out, uint64_t *h_len)
@@ -8262,22 +8264,19 @@ int dc_nyb_decompress(dc_ctx *c, const uint8_t *d_in, uint64_t m, int modify, ui
     if (!c || !d_out || !h_len || (m && !d_in)) return DC_E_ARG;
     if (m == 0) { *h_len = 0; return DC_OK; }
     uint8_t type = 0;
-    int r = read_byte(c, d_in, &type);
+    int r = read_back(c, d_in, &type);
     if (r) return r;
     if (type == 0xAF) {
         if (m < 2) { *h_len = 0; return DC_OK; }
-        if (!modify) return fsm_run<M_NYB_DEC>(c, d_in, m, m - 2, d_out, h_len, "nyb_dec_tiles");
+        if (!modify) return fsm_stream<M_NYB_DEC>(c, d_in, m, m - 2, d_out, h_len, "nyb_dec_tiles");
 #ifdef DC_AB_KERNELS
         if (c->opt_adec_v1 == 1) {   // A/B only: the one-pass single-wave decoder
             LAUNCH(c, "nyb_adec", k_nyb_adec, 1, 64, d_in, m, d_out, c->d_meta);
-            HIPCHK(hipMemcpyAsync(c->h_pinned, c->d_meta, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(hipStreamSynchronize(c->stream));
-            *h_len = c->h_pinned[0];
-            return DC_OK;
+            return read_back(c, c->d_meta, h_len);
         }
 #endif
         // tokens by the static transducer (parallel), then one wave resolves them in place
-        r = fsm_run<M_NYB_DEC>(c, d_in, m, m - 2, d_out, h_len, "nyb_tok_tiles", FsmAux{nullptr, 0, 0, 1, 1, 1});
+        r = fsm_stream<M_NYB_DEC>(c, d_in, m, m - 2, d_out, h_len, "nyb_tok_tiles", aux_tokens());
         if (r) return r;
         const uint64_t n = *h_len;
         if (n > 1 && c->opt_adec_v1 == 0) return adec_fast(c, d_out, n);   // control words + k_nyb_resolve_c
@@ -8290,9 +8289,8 @@ int dc_nyb_decompress(dc_ctx *c, const uint8_t *d_in, uint64_t m, int modify, ui
         HIPCHK(hipStreamSynchronize(c->stream));
         return DC_OK;
     }
-    bool handled = false;
-    r = copy_typed(c, d_in, m, type, d_out, h_len, &handled);
-    if (r || handled) return r;
+    r = copy_typed(c, d_in, m, type, d_out, h_len);
+    if (r) return r > 0 ? DC_OK : r;
     HIPCHK(hipMemcpyAsync(d_out, d_in, m, hipMemcpyDeviceToDevice, c->stream));   // unknown type (:806-812)
     HIPCHK(hipStreamSynchronize(c->stream));
     *h_len = m;
@@ -8302,8 +8300,8 @@ int dc_nyb_decompress(dc_ctx *c, const uint8_t *d_in, uint64_t m, int modify, ui
 int dc_small_compress(dc_ctx *c, const uint8_t *d_in, uint64_t n, uint8_t *d_out, uint64_t *h_len)
 {
     if (!c || !d_out || !h_len || (n && !d_in)) return DC_E_ARG;
-    if (n == 0) { int r = write_byte(c, d_out, ' '); if (r) return r; HIPCHK(hipStreamSynchronize(c->stream)); *h_len = 1; return DC_OK; }
-    return fsm_run<M_SMALL_ENC>(c, d_in, n, n - 1, d_out, h_len, "small_enc_tiles");
+    if (n == 0) return empty_stream(c, d_out, h_len);
+    return fsm_stream<M_SMALL_ENC>(c, d_in, n, n - 1, d_out, h_len, "small_enc_tiles");
 }
 
 int dc_small_compress_body(dc_ctx *c, const uint8_t *d_in, uint64_t len, int left_halo, uint64_t nelem,
@@ -8311,8 +8309,8 @@ int dc_small_compress_body(dc_ctx *c, const uint8_t *d_in, uint64_t len, int lef
 {
     if (!c || !d_out || !h_len || (len && !d_in) || (nelem && nelem + 1 > len)) return DC_E_ARG;
     if (nelem == 0) { *h_len = 0; return DC_OK; }
-    return left_halo ? fsm_run<M_SMALL_BODY1>(c, d_in, len, nelem, d_out, h_len, "small_body_tiles")
-                     : fsm_run<M_SMALL_BODY0>(c, d_in, len, nelem, d_out, h_len, "small_body_tiles");
+    return left_halo ? fsm_stream<M_SMALL_BODY1>(c, d_in, len, nelem, d_out, h_len, "small_body_tiles")
+                     : fsm_stream<M_SMALL_BODY0>(c, d_in, len, nelem, d_out, h_len, "small_body_tiles");
 }
 
 int dc_small_compress_body_plan(dc_ctx *c, const uint8_t *d_in, uint64_t len, int left_halo, uint64_t nelem,
@@ -8320,10 +8318,8 @@ int dc_small_compress_body_plan(dc_ctx *c, const uint8_t *d_in, uint64_t len, in
 {
     if (!c || !h_len || (len && !d_in) || (nelem && nelem + 1 > len)) return DC_E_ARG;
     if (nelem == 0) { c->fsm_in = nullptr; *h_len = 0; return DC_OK; }
-    return left_halo ? fsm_run<M_SMALL_BODY1>(c, d_in, len, nelem, nullptr, h_len, "small_body_tiles",
-                                              FsmAux{nullptr, 0, 0, 1, 1}, nullptr, false)
-                     : fsm_run<M_SMALL_BODY0>(c, d_in, len, nelem, nullptr, h_len, "small_body_tiles",
-                                              FsmAux{nullptr, 0, 0, 1, 1}, nullptr, false);
+    return left_halo ? fsm_stream<M_SMALL_BODY1>(c, d_in, len, nelem, PLAN_ONLY, h_len, "small_body_tiles")
+                     : fsm_stream<M_SMALL_BODY0>(c, d_in, len, nelem, PLAN_ONLY, h_len, "small_body_tiles");
 }
 
 int dc_small_compress_body_write(dc_ctx *c, const uint8_t *d_in, uint64_t len, int left_halo, uint64_t nelem,
@@ -8339,7 +8335,7 @@ int dc_small_decompress_body(dc_ctx *c, const uint8_t *d_in, uint64_t m, uint8_t
 {
     if (!c || !d_out || !h_len || (m && !d_in)) return DC_E_ARG;
     if (m == 0) { *h_len = 0; return DC_OK; }
-    return fsm_run<M_SMALL_DBODY>(c, d_in, m, m, d_out, h_len, "small_dbody_tiles");
+    return fsm_stream<M_SMALL_DBODY>(c, d_in, m, m, d_out, h_len, "small_dbody_tiles");
 }
 
 int dc_small_huff_decode(dc_ctx *c, const uint32_t *d_words, uint64_t bit_base, uint64_t words,
@@ -8356,13 +8352,12 @@ int dc_small_huff_decode(dc_ctx *c, const uint32_t *d_words, uint64_t bit_base, 
         return r ? r : dc_small_decompress(c, d_m, m, d_out, h_len);
     }
     const uint64_t groups = dc_huff_sync_groups(m, 64);
-    if (ensure((void **)&c->d_gexp, &c->gexp_cap, (groups + 2) * sizeof(uint32_t))) return DC_E_HIP;
-    int r = decode_impl(c, d_words, bit_base, nullptr, words, d_sync_base, d_sync_len, 64, m, d_table, d_m, c->d_gexp);
+    if (ensure(c->ws.gexp, (groups + 2) * sizeof(uint32_t))) return DC_E_HIP;
+    int r = decode_impl(c, d_words, bit_base, nullptr, words, d_sync_base, d_sync_len, 64, m, d_table, d_m, c->ws.gexp);
     if (r) return r;
-    r = fsm_run<M_SMALL_DEC>(c, d_m, m, m - 2, d_out, h_len, "small_dec_tiles", FsmAux{nullptr, 0, 0, 1, 1}, nullptr,
-                             true, c->d_gexp, groups);
-    if (r == DC_E_STREAM) return dc_small_decompress(c, d_m, m, d_out, h_len);   // not a type-8 stream
-    return r;
+    r = fsm_stream<M_SMALL_DEC>(c, d_m, m, m - 2, d_out, h_len, "small_dec_tiles", aux_whole(),
+                                summ_decoder(c->ws.gexp, groups));
+    return r == DC_E_STREAM ? dc_small_decompress(c, d_m, m, d_out, h_len) : r;   // (not a type-8 stream)
 }
 
 int dc_small_decompress(dc_ctx *c, const uint8_t *d_in, uint64_t m, uint8_t *d_out, uint64_t *h_len)
@@ -8370,15 +8365,14 @@ int dc_small_decompress(dc_ctx *c, const uint8_t *d_in, uint64_t m, uint8_t *d_o
     if (!c || !d_out || !h_len || (m && !d_in)) return DC_E_ARG;
     if (m == 0) { *h_len = 0; return DC_OK; }
     uint8_t type = 0;
-    int r = read_byte(c, d_in, &type);
+    int r = read_back(c, d_in, &type);
     if (r) return r;
     if (type == 8) {
         if (m < 2) { *h_len = 0; return DC_OK; }
-        return fsm_run<M_SMALL_DEC>(c, d_in, m, m - 2, d_out, h_len, "small_dec_tiles");
+        return fsm_stream<M_SMALL_DEC>(c, d_in, m, m - 2, d_out, h_len, "small_dec_tiles");
     }
-    bool handled = false;
-    r = copy_typed(c, d_in, m, type, d_out, h_len, &handled);
-    if (r || handled) return r;
+    r = copy_typed(c, d_in, m, type, d_out, h_len);
+    if (r) return r > 0 ? DC_OK : r;
     *h_len = 0;   // "invalid compressed data": empty output (small_compression.c:497-499)
     return DC_OK;
 }

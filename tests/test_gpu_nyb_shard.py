@@ -244,7 +244,7 @@ def test_body_write_argument_product(torch_cuda, codecs, variant, modify):
 @pytest.mark.parametrize("variant", VARIANTS, ids=VIDS)
 def test_body_write_of_a_shard_of_no_elements(torch_cuda, codecs, variant):
     """len = 1: the state passes through; one byte, d_in[0], only when a nybble is pending and the
-    shard ends the stream (the odd tail), else nothing. (fsm_run's ntiles == 0 branch counts that
+    shard ends the stream (the odd tail), else nothing. (fsm_count's ntiles == 0 branch counts that
     byte in the length and no writer has an element to store it from: dc_nyb_body_write copies it.)"""
     _, in_off, wtile_off = variant
     codec = codecs[1 if wtile_off else 0]
@@ -283,7 +283,7 @@ LAST_COUNTS = tuple(range(1, 41)) + (TILE, TILE + 1)
 
 @pytest.mark.parametrize("in_off", [0, 3], ids=["walk2", "walk3"])
 def test_adaptive_plan_last_rank_of_a_first_touch(torch_cuda, codec, in_off):
-    """h_plan[4] is d_rk[len - 2], where k_mtf_walk leaves 0xFE for a first touch and k_mtf_resolve
+    """h_plan[4] is ws.rk[len - 2], where k_mtf_walk leaves 0xFE for a first touch and k_mtf_resolve
     settles the tile's last element: shards of 1..40 elements, and of a tile and one more, whose
     last element's byte 'Z' is nowhere before it in the shard and sits in its context's entry list
     at each rank in turn, or not at all. The write that follows carries that rank out."""

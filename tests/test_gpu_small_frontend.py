@@ -365,7 +365,7 @@ def test_plan_then_write(torch_cuda, codec):
 
 def test_one_context_mixed(torch_cuda):
     """Encode, body, decode, then an encode of another size on one context: each equals the result
-    of a fresh context and the model (stale d_summ, d_entry or d_meta would show)."""
+    of a fresh context and the model (stale ws.summ, ws.entry or d_meta would show)."""
     from data_compression_amd.device import Codec
     torch = torch_cuda
     big, xb = _place(torch, 7, fm.ENC_N, lambda addr: fm.planted("pair_straddles_edge", addr)[0])
