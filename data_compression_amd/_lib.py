@@ -145,6 +145,13 @@ def _declare_core(L):
         "dc_huff_batch_range_args": ([u64, u64, u64, u64, u64, u64], i32),
         "dc_huff_decode_batch_ranges": ([vp, C.POINTER(HBatch), P, P, P, P, P, u64, P, u64, P], i32),
         "dc_huff_decode_batch_shared_ranges": ([vp, C.POINTER(HBatch), P, P, P, P, P, P, u64, P, u64, P], i32),
+        "dc_huff_batch_set_table_ok": ([P, i32], i32),
+        "dc_huff_batch_set_select": ([vp, P, P, u64, i32, P, u32, P, P, P, P], i32),
+        "dc_huff_encode_batch_set": ([vp, P, P, u64, P, u32, P, C.POINTER(HBatch)], i32),
+        "dc_huff_decode_batch_set": ([vp, C.POINTER(HBatch), P, u32, P, P, P, u64], i32),
+        "dc_huff_decode_batch_set_scatter": ([vp, C.POINTER(HBatch), P, u32, P, P, P, P, u64], i32),
+        "dc_huff_decode_batch_set_ranges": ([vp, C.POINTER(HBatch), P, u32, P, P, P, P, P, P, u64, P, u64, P], i32),
+        "dc_huff_batch_set_hist": ([vp, P, P, u64, P, u32, P], i32),
         "dc_huff_decode_redo_count": ([vp, C.POINTER(u64)], i32),
         "dc_huff_base64url": ([vp, P, u64, u64, P], i32),
         "dc_huff_text_bits": ([i32, i32], i32),

@@ -21,6 +21,7 @@
 #include "dc_nyb_batch_bound.h"
 #include "dc_small_batch_bound.h"
 #include "dc_batch_range.h"
+#include "dc_batch_set.h"
 #include "dc_huff_limit.h"
 #include "dc_crc32.h"
 
@@ -6264,6 +6265,7 @@ __global__ __launch_bounds__(256) void k_copy_probe(const uint4 *__restrict__ sr
 #include "dc_batch_lens_kernels.inc"
 #include "dc_batch_shared_kernels.inc"
 #include "dc_batch_range_kernels.inc"
+#include "dc_batch_set_kernels.inc"
 #include "dc_nyb_batch_kernels.inc"
 #include "dc_small_batch_kernels.inc"
 #include "dc_crc_kernels.inc"
@@ -7583,6 +7585,102 @@ int dc_huff_decode_batch_shared_ranges(dc_ctx *c, const dc_hbatch *b, const dc_d
     const uint64_t g2 = hbatch_grid(c, (nranges + 3) / 4, 512);   // a workgroup takes four ranges at a time
     LAUNCH(c, "hbs_decode_ranges", k_hbs_decode_ranges, g2, HB_THREADS,
            hbatch_dec_args(b, d_out, nullptr, nullptr, out_cap, d_rstatus, first), R, nranges, d_table);
+    return DC_OK;
+}
+
+// the table-set mode (dc_batch_set_kernels.inc): no d_lens; a set of K records in the table's place and
+// a record number per segment. work: the call has segments or ranges to take.
+static int hbatch_set_args(const uint8_t *d_set, uint32_t K, const uint8_t *d_tid, bool work)
+{
+    if (K == 0 || K > DC_BATCH_SET_MAX || ((uintptr_t)d_set & 15)) return DC_E_ARG;
+    if (work && (!d_set || !d_tid)) return DC_E_ARG;
+    return DC_OK;
+}
+
+int dc_huff_batch_set_table_ok(const uint8_t *lens256, int n_ary)
+{
+    return lens256 ? dc_batch_set_table_ok(lens256, n_ary, 0) : 0;
+}
+
+// the plan's LDS is 17.5 KiB: 8 workgroups a CU
+int dc_huff_batch_set_select(dc_ctx *c, const uint8_t *d_in, const uint64_t *d_in_off, uint64_t count, int n_ary,
+                             const uint8_t *d_set, uint32_t K, uint8_t *d_tid, uint8_t *d_mode, uint32_t *d_bits,
+                             int32_t *d_status)
+{
+    if (!c || n_ary < 2 || n_ary > 256) return DC_E_ARG;
+    if (const int r = hbatch_set_args(d_set, K, d_tid, count != 0)) return r;
+    if (count == 0) return DC_OK;
+    if (!d_in_off || !d_mode || !d_bits || !d_status || count > DC_RANGES_MAX) return DC_E_ARG;
+    unsigned long long *first;
+    if (const int r = hbatch_begin(c, 0, &first)) return r;
+    LAUNCH(c, "hbm_plan", k_hbm_plan, hbatch_grid(c, count, 2048), HB_THREADS, d_in, d_in_off, count, n_ary, hbatch_w(n_ary),
+           64u, d_set, K, d_tid, d_mode, d_bits, (uint64_t *)nullptr, (uint64_t *)nullptr, d_status, first);
+    return DC_OK;
+}
+
+int dc_huff_encode_batch_set(dc_ctx *c, const uint8_t *d_in, const uint64_t *d_in_off, uint64_t count,
+                             const uint8_t *d_set, uint32_t K, uint8_t *d_tid, const dc_hbatch *b)
+{
+    if (const int r = hbatch_set_args(d_set, K, d_tid, count != 0)) return r;
+    unsigned long long *first;
+    if (const int r = hbatch_encode_begin(c, b, false, d_in_off, count, &first)) return r > 0 ? DC_OK : r;
+    uint64_t *const psize = c->ws.hb + 2, *const nch = c->ws.hb + 2 + count;
+    const uint64_t g8 = hbatch_grid(c, count, 2048), g2 = hbatch_grid(c, count, 512);   // the pack's stage allows 2
+    LAUNCH(c, "hbm_plan", k_hbm_plan, g8, HB_THREADS, d_in, d_in_off, count, (int)b->n_ary, hbatch_w(b->n_ary), b->sync_syms,
+           d_set, K, d_tid, b->d_mode, b->d_bits, psize, nch, b->d_status, first);
+    if (const int r = hbatch_scans(c, b, psize, nch)) return r;
+    LAUNCH(c, "hbm_pack", k_hbm_pack, g2, HB_THREADS, d_in, d_in_off, count, (int)b->n_ary, hbatch_w(b->n_ary), b->sync_syms,
+           d_set, K, (const uint8_t *)d_tid, (const uint8_t *)b->d_mode, (const uint64_t *)b->d_pay_off, b->d_payload,
+           b->payload_cap, (const uint64_t *)b->d_sync_off, b->d_sync_len, b->sync_cap, b->d_status, first);
+    return DC_OK;
+}
+
+int dc_huff_decode_batch_set_scatter(dc_ctx *c, const dc_hbatch *b, const uint8_t *d_set, uint32_t K, const uint8_t *d_tid,
+                                     uint8_t *d_out, const uint64_t *d_out_beg, const uint64_t *d_out_end, uint64_t out_cap)
+{
+    if (const int r = hbatch_set_args(d_set, K, d_tid, b && b->count != 0)) return r;
+    unsigned long long *first;
+    if (const int r = hbatch_decode_begin(c, b, false, d_out, d_out_beg, d_out_end, out_cap, &first)) return r > 0 ? DC_OK : r;
+    const uint64_t g2 = hbatch_grid(c, (b->count + 3) / 4, 512);   // a workgroup takes four segments at a time
+    LAUNCH(c, "hbm_decode", k_hbm_decode, g2, HB_THREADS, hbatch_dec_args(b, d_out, d_out_beg, d_out_end, out_cap, b->d_status, first),
+           b->count, d_set, K, d_tid);
+    return DC_OK;
+}
+
+int dc_huff_decode_batch_set(dc_ctx *c, const dc_hbatch *b, const uint8_t *d_set, uint32_t K, const uint8_t *d_tid,
+                             uint8_t *d_out, const uint64_t *d_out_off, uint64_t out_cap)
+{
+    if (b && b->count && !d_out_off) return DC_E_ARG;
+    return dc_huff_decode_batch_set_scatter(c, b, d_set, K, d_tid, d_out, d_out_off, d_out_off + 1, out_cap);
+}
+
+int dc_huff_decode_batch_set_ranges(dc_ctx *c, const dc_hbatch *b, const uint8_t *d_set, uint32_t K, const uint8_t *d_tid,
+                                    const uint64_t *d_seg_off, const uint64_t *d_seg, const uint64_t *d_first,
+                                    const uint64_t *d_count, const uint64_t *d_out_off, uint64_t nranges, uint8_t *d_out,
+                                    uint64_t out_cap, int32_t *d_rstatus)
+{
+    if (const int r = hbatch_set_args(d_set, K, d_tid, nranges != 0)) return r;
+    unsigned long long *first;
+    if (const int r = hbatch_ranges_begin(c, b, false, d_seg_off, d_seg, d_first, d_count, d_out_off, nranges, d_out, out_cap,
+                                          d_rstatus, &first))
+        return r > 0 ? DC_OK : r;
+    const HbRangeArgs R{d_seg_off, d_seg, d_first, d_count, d_out_off, b->count};
+    const uint64_t g2 = hbatch_grid(c, nranges, 512);   // LDS-bound: 2 per CU
+    LAUNCH(c, "hbm_decode_ranges", k_hbm_decode_ranges, g2, HB_THREADS,
+           hbatch_dec_args(b, d_out, nullptr, nullptr, out_cap, d_rstatus, first), R, nranges, d_set, K, d_tid);
+    return DC_OK;
+}
+
+// 64 KiB of LDS counters: 2 workgroups a CU
+int dc_huff_batch_set_hist(dc_ctx *c, const uint8_t *d_in, const uint64_t *d_in_off, uint64_t count, const uint8_t *d_tid,
+                           uint32_t K, uint64_t *d_hist)
+{
+    if (!c || K == 0 || K > DC_BATCH_SET_MAX || !d_hist) return DC_E_ARG;
+    if (count && (!d_in_off || !d_tid || count > DC_RANGES_MAX)) return DC_E_ARG;
+    HIPCHK(hipMemsetAsync(d_hist, 0, (size_t)K * 256 * sizeof(uint64_t), c->stream));
+    if (count == 0) return DC_OK;
+    LAUNCH(c, "hbm_hist", k_hbm_hist, hbatch_grid(c, count, 512), HB_THREADS, d_in, d_in_off, count, d_tid, K,
+           reinterpret_cast<unsigned long long *>(d_hist));
     return DC_OK;
 }
 

@@ -729,7 +729,7 @@ class Codec:
         return v
 
     def encode_batch(self, x, offsets, n_ary: int = 2, sync_syms: int = 64, payload=None, sync_len=None,
-                     payload_cap=None, sync_cap=None, table=None, max_bits=None, checksum: bool = False):
+                     payload_cap=None, sync_cap=None, table=None, max_bits=None, checksum: bool = False, table_set=None):
         """dc_huff_encode_batch: segment i = x[offsets[i]:offsets[i+1]] (device uint8 x, int64
         offsets of count + 1 entries, any alignment, each segment <= 65536 bytes) coded under a
         table of its own, or stored when that is not smaller. Asynchronous, no host read; the
@@ -748,9 +748,20 @@ class Codec:
         checksum (any mode): the result also carries "crc", the CRC-32 of every input segment
         (crc32_batch over the same offsets: one more launch), for decode_batch(verify=True). A
         segment whose offsets decrease has crc 0 and fails the encode anyway. The default
-        leaves the call and its result exactly as they are without it."""
+        leaves the call and its result exactly as they are without it.
+        table_set: a K x 256 uint8 device tensor of lens records (table_set(), batch_table_set()):
+        every segment is coded under the record of the set that costs it the fewest bits among
+        those with a code for each of its bytes, the lowest of equal ones
+        (dc_huff_encode_batch_set), or stored when none has or none is smaller. No table work
+        per segment beyond that choice and no lens record: the result carries "table_set":
+        table_set, "tid" (uint8, count: the record of each segment) and "lens": None. Exclusive
+        with table= and max_bits= (a ValueError): cap the records where they are made."""
         if x.dtype != torch.uint8 or not x.is_contiguous():
             raise ValueError("encode_batch input: contiguous uint8")
+        if table_set is not None:
+            if table is not None or max_bits is not None:
+                raise ValueError("encode_batch: table_set excludes table= and max_bits= (cap the set's records in table())")
+            self._table_set(table_set, "encode_batch")
         if table is not None and max_bits is not None:
             raise ValueError("encode_batch: max_bits caps the per-segment tables; cap a shared table in batch_table()")
         max_digits = self.max_digits(n_ary, max_bits)
@@ -760,7 +771,7 @@ class Codec:
         payload = payload if payload is not None else self._t(max(pb, 16))
         sync_len = sync_len if sync_len is not None else self._t(max(sb, 1), torch.int16)
         enc = {"count": count, "n_ary": n_ary, "S": sync_syms, "offsets": offsets, "total": x.numel(),
-               "lens": self._t(max(count, 1) * 256).view(max(count, 1), 256)[:count] if table is None else None,
+               "lens": self._t(max(count, 1) * 256).view(max(count, 1), 256)[:count] if table is None and table_set is None else None,
                "mode": self._t(max(count, 1))[:count],
                "bits": self._t(max(count, 1), torch.int32)[:count], "pay_off": self._t(count + 1, torch.int64),
                "payload": payload, "sync_off": self._t(count + 1, torch.int64), "sync_len": sync_len,
@@ -769,6 +780,13 @@ class Codec:
         enc["payload_cap"], enc["sync_cap"] = int(b.payload_cap), int(b.sync_cap)
         if checksum:   # (before the encode: batch_status() after the call is the encode's)
             enc["crc"] = self.crc32_batch(x, offsets=offsets)[0]
+        if table_set is not None:
+            enc["table_set"] = table_set
+            enc["tid"] = self._t(max(count, 1))[:count]
+            check("dc_huff_encode_batch_set",
+                  self.L.dc_huff_encode_batch_set(self.ctx, _ptr(x), _ptr(offsets), count, _ptr(table_set),
+                                                  table_set.shape[0], _ptr(enc["tid"]), C.byref(b)))
+            return enc
         if table is not None:
             enc["table"] = table
             check("dc_huff_encode_batch_shared",
@@ -784,8 +802,9 @@ class Codec:
     def encode_blocks(self, x, block: int = 65536, **kw):
         """encode_batch of x cut into independent blocks of `block` bytes (the last shorter),
         a table each: the reference's own block design (n_ary_huffman.c:1210-1255); with
-        table=..., all under that one table; with max_bits=..., each table capped; with
-        checksum=True, the CRC-32 of every block in "crc"."""
+        table=..., all under that one table; with table_set=..., each under the cheapest record
+        of the set; with max_bits=..., each table capped; with checksum=True, the CRC-32 of every
+        block in "crc"."""
         if not 0 < block <= self.SEG_MAX:
             raise ValueError("encode_blocks: 0 < block <= 65536")
         return self.encode_batch(x, self._block_offsets(x, block), **kw)
@@ -797,7 +816,8 @@ class Codec:
         outputs may lie anywhere in out (dc_huff_decode_batch_scatter). Default: the segments
         back to back from 0. Asynchronous; returns (out, out_off). Per-segment outcome in
         enc["status"], the first failure by batch_status(). A batch encoded under a shared
-        table (enc["table"]) is decoded under it (dc_huff_decode_batch_shared).
+        table (enc["table"]) is decoded under it (dc_huff_decode_batch_shared), one encoded under a
+        table set (enc["table_set"], enc["tid"]) under its records (dc_huff_decode_batch_set).
         verify: after the decode, the CRC-32 of every decoded segment against enc["crc"]
         (encode_batch(checksum=True); a ValueError without it), in either layout: a segment that
         decoded with DC_OK to other bytes than went in (a damaged stored segment, a code
@@ -807,7 +827,6 @@ class Codec:
         if verify and enc.get("crc") is None:
             raise ValueError("decode_batch: verify=True needs enc[\"crc\"] (encode_batch(..., checksum=True))")
         count = enc["count"]
-        table = enc.get("table")
         if out_off is None:
             out_off = enc["offsets"] - enc["offsets"][:1]
         out_off = self._i64(out_off, (count, count + 1), "decode_batch out_off")
@@ -817,15 +836,15 @@ class Codec:
                 raise ValueError("decode_batch: segment starts alone need an output buffer")
         buf = self._u8_out(out, "decode_batch")
         b = self._hbatch(enc, enc["payload_cap"], enc["sync_cap"])
-        tab = () if table is None else (_ptr(table),)
+        tab, mid = self._batch_table_args(enc)
         if out_off.numel() == count + 1:
-            fn = "dc_huff_decode_batch" if table is None else "dc_huff_decode_batch_shared"
+            fn = "dc_huff_decode_batch" + mid
             check(fn, getattr(self.L, fn)(self.ctx, C.byref(b), *tab, _ptr(buf), _ptr(out_off), buf.numel()))
             if verify:
                 self.crc32_verify_batch(buf, enc["crc"], enc["status"], offsets=out_off)
         else:
             end = out_off + (enc["offsets"][1:] - enc["offsets"][:-1])
-            fn = "dc_huff_decode_batch_scatter" if table is None else "dc_huff_decode_batch_shared_scatter"
+            fn = "dc_huff_decode_batch" + mid + "_scatter"
             check(fn, getattr(self.L, fn)(self.ctx, C.byref(b), *tab, _ptr(buf), _ptr(out_off), _ptr(end), buf.numel()))
             if verify:
                 self.crc32_verify_batch(buf, enc["crc"], enc["status"], beg=out_off, end=end)
@@ -833,7 +852,8 @@ class Codec:
 
     def decode_batch_ranges(self, enc, seg, first, count, out=None, out_off=None):
         """Byte ranges of segments in one call (dc_huff_decode_batch_ranges, or
-        dc_huff_decode_batch_shared_ranges when enc has a "table"): range r = bytes [first[r],
+        dc_huff_decode_batch_shared_ranges when enc has a "table", dc_huff_decode_batch_set_ranges
+        when it has a "table_set"): range r = bytes [first[r],
         first[r] + count[r]) of segment seg[r] of the dict encode_batch returned -> out[out_off[r]
         ..). seg / first / count / out_off: int64 device tensors (read by the kernels: a gather
         list computed on the GPU is used as it is) or Python sequences. enc["offsets"] gives the
@@ -850,9 +870,8 @@ class Codec:
         nr = count.numel()
         status = self._t(max(nr, 1), torch.int32)[:nr]
         b = self._hbatch(enc, enc["payload_cap"], enc["sync_cap"])
-        table = enc.get("table")
-        tab = () if table is None else (_ptr(table),)
-        fn = "dc_huff_decode_batch_ranges" if table is None else "dc_huff_decode_batch_shared_ranges"
+        tab, mid = self._batch_table_args(enc)
+        fn = "dc_huff_decode_batch" + mid + "_ranges"
         check(fn, getattr(self.L, fn)(self.ctx, C.byref(b), *tab, _ptr(enc["offsets"]), _ptr(seg), _ptr(first), _ptr(count),
                                       _ptr(out_off), nr, _ptr(buf), out.numel(), _ptr(status)))
         return out, out_off, status
@@ -899,6 +918,122 @@ class Codec:
         if cover:
             hist.clamp_(min=1)
         return self.table(hist, n_ary, max_bits=max_bits)
+
+    # ---- table sets: K tables, each segment under its cheapest (dc_gpu.h "Huffman batch v1, table set") ----
+    SET_MAX = 64   # DC_BATCH_SET_MAX
+
+    def _table_set(self, ts, name):
+        if not hasattr(ts, "data_ptr") or ts.dtype != torch.uint8 or not ts.is_cuda or not ts.is_contiguous() \
+                or ts.dim() != 2 or ts.shape[1] != 256 or not 1 <= ts.shape[0] <= self.SET_MAX:
+            raise ValueError(f"{name}: a table set is a contiguous K x 256 uint8 device tensor, 1 <= K <= {self.SET_MAX}")
+        return ts
+
+    @staticmethod
+    def _batch_table_args(enc):
+        """What a decode call takes between the batch and its output, and the part of its name
+        that says so: nothing (own tables), the shared table, or the set, K and tid."""
+        if enc.get("table_set") is not None:
+            ts = enc["table_set"]
+            return (_ptr(ts), ts.shape[0], _ptr(enc["tid"])), "_set"
+        if enc.get("table") is not None:
+            return (_ptr(enc["table"]),), "_shared"
+        return (), ""
+
+    def table_set(self, records, n_ary: int):
+        """A table set for encode_batch(..., table_set=): the K x 256 uint8 device tensor of the K
+        records, each either an array of code lengths in digits (its first 256 entries are used;
+        what table_get_lengths returns, or a row of enc["lens"]) or a device table of that n_ary
+        (read back through table_get_lengths). ValueError for K outside 1..64. A record that is
+        no code at n_ary (dc_huff_batch_set_table_ok) is legal: no segment chooses it."""
+        records = list(records)
+        if not 1 <= len(records) <= self.SET_MAX:
+            raise ValueError(f"table_set: 1 <= K <= {self.SET_MAX} records, not {len(records)}")
+        if not 2 <= int(n_ary) <= 256:
+            raise ValueError("table_set: 2 <= n_ary <= 256")
+        rows = np.zeros((len(records), 256), np.uint8)
+        for k, r in enumerate(records):
+            if hasattr(r, "data_ptr") and r.is_cuda and r.dtype == torch.uint8 and r.numel() == self.table_bytes:
+                r = self.table_get_lengths(r)
+            elif hasattr(r, "data_ptr"):
+                r = r.cpu().numpy()
+            r = np.asarray(r).reshape(-1)[:256]
+            if r.size and (r.min() < 0 or r.max() > 255):
+                raise ValueError(f"table_set: record {k} holds a length outside 0..255")
+            rows[k, : r.size] = r
+        return torch.from_numpy(rows).to(f"cuda:{self.device}")
+
+    def batch_set_select(self, x, offsets, ts, n_ary: int = 2):
+        """dc_huff_batch_set_select: (tid, mode, bits, status), device tensors of count entries
+        (uint8, uint8, int32, int32), exactly what encode_batch(x, offsets, n_ary, table_set=ts)
+        puts in its result under those names, and nothing else: the plan alone, one launch,
+        asynchronous. sum(ceil(bits / 8) rounded up to 16) sizes the payload before an encode."""
+        if x.dtype != torch.uint8 or not x.is_contiguous():
+            raise ValueError("batch_set_select input: contiguous uint8")
+        self._table_set(ts, "batch_set_select")
+        offsets = self._i64(offsets, range(1, 1 << 62), "batch_set_select offsets")
+        count = offsets.numel() - 1
+        tid, mode = self._t(max(count, 1))[:count], self._t(max(count, 1))[:count]
+        bits, status = self._t(max(count, 1), torch.int32)[:count], self._t(max(count, 1), torch.int32)[:count]
+        check("dc_huff_batch_set_select",
+              self.L.dc_huff_batch_set_select(self.ctx, _ptr(x), _ptr(offsets), count, n_ary, _ptr(ts), ts.shape[0],
+                                              _ptr(tid), _ptr(mode), _ptr(bits), _ptr(status)))
+        return tid, mode, bits, status
+
+    def batch_set_hist(self, x, offsets, tid, K: int):
+        """dc_huff_batch_set_hist: the int64 K x 256 device tensor whose row k counts the bytes of
+        the segments with tid[i] == k (tid: uint8 device tensor of count entries); segments with
+        tid[i] >= K or bad offsets are skipped. One launch, asynchronous."""
+        if x.dtype != torch.uint8 or not x.is_contiguous():
+            raise ValueError("batch_set_hist input: contiguous uint8")
+        if not 1 <= K <= self.SET_MAX:
+            raise ValueError(f"batch_set_hist: 1 <= K <= {self.SET_MAX}")
+        offsets = self._i64(offsets, range(1, 1 << 62), "batch_set_hist offsets")
+        count = offsets.numel() - 1
+        if tid.dtype != torch.uint8 or not tid.is_cuda or not tid.is_contiguous() or tid.numel() != count:
+            raise ValueError("batch_set_hist tid: a contiguous uint8 device tensor of count entries")
+        hist = self._t(K * 256, torch.int64).view(K, 256)
+        check("dc_huff_batch_set_hist",
+              self.L.dc_huff_batch_set_hist(self.ctx, _ptr(x), _ptr(offsets), count, _ptr(tid), K, _ptr(hist)))
+        return hist
+
+    def batch_table_set(self, x, offsets, k: int, n_ary: int = 2, max_bits=12, iters: int = 2):
+        """Train a table set of k records on the segments x[offsets[i]:offsets[i+1]] (k-means on
+        code cost): the K x 256 uint8 device tensor for encode_batch(..., table_set=). Reads the
+        device between its steps: a call for set-up time, not for the hot path.
+        Record 0 is batch_table(x, n_ary, max_bits, cover=True): it has a code for every byte
+        value, is never replaced, and so makes every segment codable. Records 1..k-1 start from
+        the histograms of k - 1 contiguous runs of segments (segment i in run i (k - 1) // count),
+        then `iters` times: every segment selects its record (batch_set_select), the histogram of
+        each record's segments is taken (batch_set_hist), and records 1..k-1 become the tables of
+        theirs (table(hist, max_bits=)); a record no segment chose becomes 256 zeros.
+        Guaranteed: with record 0 in the set, no segment takes more bits than under record 0
+        alone, so the batch is never larger than encode_batch(table=record 0)'s, whatever the
+        other records are. Not guaranteed: that a further round makes the batch smaller (a
+        record is refitted to the segments that chose it, and bytes only the others hold lose
+        their codes), or that k records beat k - 1. Deterministic: the same input gives the same set."""
+        if not 1 <= k <= self.SET_MAX:
+            raise ValueError(f"batch_table_set: 1 <= k <= {self.SET_MAX}")
+        if x.dtype != torch.uint8 or not x.is_contiguous():
+            raise ValueError("batch_table_set input: contiguous uint8")
+        offsets = self._i64(offsets, range(1, 1 << 62), "batch_table_set offsets")
+        count = offsets.numel() - 1
+        rows = np.zeros((k, 256), np.uint8)
+        rows[0] = self.table_get_lengths(self.batch_table(x, n_ary, max_bits, cover=True))[:256]
+        if k == 1 or count == 0:
+            return torch.from_numpy(rows).to(f"cuda:{self.device}")
+
+        def refit(tid):   # records 1..k-1 from the histograms of their segments
+            hist = self.batch_set_hist(x, offsets, tid, k)
+            filled = (hist.sum(dim=1) > 0).cpu().numpy()
+            for j in range(1, k):
+                rows[j] = self.table_get_lengths(self.table(hist[j], n_ary, max_bits=max_bits))[:256] if filled[j] else 0
+            return torch.from_numpy(rows).to(f"cuda:{self.device}")
+
+        i = torch.arange(count, dtype=torch.int64, device=f"cuda:{self.device}")
+        ts = refit((1 + i * (k - 1) // count).to(torch.uint8))
+        for _ in range(iters):
+            ts = refit(self.batch_set_select(x, offsets, ts, n_ary)[0])
+        return ts
 
     def table_get_lengths(self, tab):
         """dc_huff_table_get_lengths: the table's lengths in digits, entries 0 ..

@@ -623,6 +623,79 @@ int dc_huff_decode_batch_shared_ranges(dc_ctx *ctx, const dc_hbatch *batch, cons
                                        const uint64_t *d_seg_off, const uint64_t *d_seg, const uint64_t *d_first,
                                        const uint64_t *d_count, const uint64_t *d_out_off, uint64_t nranges,
                                        uint8_t *d_out, uint64_t out_cap, int32_t *d_rstatus);
+/* ---- Huffman batch v1, table set: K tables, each segment under its cheapest ---------------------
+ * The middle ground between a table per segment and one table for all
+ * (n_ary_huffman.c:1210-1255: "remembering the last 2 or so Huffman tables ... emit a reference
+ * indicating 'same as #2 table'"; regions of text, upper-case text and base-64 each under a table
+ * that fits): a mode of the same dc_hbatch for a batch of mixed content. No format changes.
+ * The set: K lens records, 1 <= K <= DC_BATCH_SET_MAX, d_set (u8[256 K], 16-B aligned). Record k
+ * is 256 code lengths in digits, exactly a lens record of the own-table batch; its code is that
+ * of dc_huff_table_lengths on those lengths with symbols 256..258 at 0. Each segment carries one
+ * more byte, d_tid[i] (u8[count]): the record it is coded under. dc_hbatch does not change:
+ * d_set, K and d_tid are call arguments; batch->d_lens is neither read nor written, may be NULL.
+ * With w = ceil(log2 n_ary):
+ *   valid    record k is valid when every length L has L w <= 32 and the lengths satisfy Kraft:
+ *            with Lmax the longest, the sum over L_s > 0 of n^(Lmax - L_s) is <= n^Lmax
+ *            (dc_huff_batch_set_table_ok, csrc/dc_batch_set.h). 256 zeros are valid and code nothing.
+ *   usable   record k is usable for segment i when it is valid and L_k[s] > 0 for every byte
+ *            value s the segment holds.
+ *   select   for a segment of len > 0 with histogram h, cost_k = sum h[s] L_k[s] w. The segment
+ *            takes the usable k of least cost, the lowest k of equal costs: tid[i] = k, or 0
+ *            when no record is usable. mode[i] = 1 when a record is usable and cost < 8 len;
+ *            else 0 (stored, bits = 8 len). len 0: stored, 0 bits, tid 0. An invalid record is
+ *            never chosen and never an error: a set of invalid records stores every segment.
+ * Everything else is batch v1's: bits, the payload (a mode-1 payload is bit for bit what
+ * dc_huff_encode_batch_shared writes for the segment under dc_huff_table_lengths(record tid[i])),
+ * pay_off, sync_len, sync_off, the zero pads, both bound functions, the statuses and their order,
+ * "nothing is written for a failed segment or past a cap" (a DC_E_ARG segment writes no tid
+ * either), the first-failure slot, DC_OPT_BATCH_GRID, no host read, launches that do not depend
+ * on count.
+ * Decode: batch v1's tests in its order (output range, cap, the record); then for a mode-1
+ * segment DC_E_STREAM when tid[i] >= K or record tid[i] gives no code (a length over
+ * DC_MAX_DIGITS or a code over 32 bits: the own-table decoder's rule; Kraft is the encoder's
+ * guard alone). A stored segment never reads tid or the set; a bad tid fails its own segment only.
+ * As in every mode a chunk must decode to exactly its symbols in exactly its bits, which a wrong
+ * but valid record can pass: keep a CRC-32 per segment (dc_crc32_batch) to see that.
+ * Host argument rules are the shared mode's with the set in the table's place: DC_E_ARG, nothing
+ * launched, for K == 0, K > DC_BATCH_SET_MAX, d_set not 16-B aligned, n_ary outside 2..256, or
+ * d_set / d_tid NULL with work to do; count 0 (ranges: nranges 0) returns DC_OK without a launch.
+ * dc_huff_batch_status answers for all of these calls.
+ * What to store: the K records once (dc_huff_batch_lens_pack takes K records as it takes count),
+ * then per segment mode, bits and tid, the payload and the u16 index.
+ * Cost. The plan keeps the set (<= 16 KiB) in LDS; pack, decode and ranges give each workgroup a
+ * contiguous run of segments or ranges and rebuild a table only when tid differs from the one
+ * before, so data made of long regions pays a table build per region, not per segment. The
+ * whole-segment decode deals segments four consecutive at a time as the shared mode does: four of
+ * at most 8 KiB each whose coded ones name one record go one to a wave, any other group one
+ * segment after the other to the workgroup. */
+#define DC_BATCH_SET_MAX 64
+/* pure host: 1 when the 256 lengths are a valid record at n_ary, else 0 (also for a NULL pointer
+ * or n_ary outside 2..256) */
+int dc_huff_batch_set_table_ok(const uint8_t *lens256, int n_ary);
+/* the plan alone, one launch: d_tid, d_mode, d_bits, d_status exactly as the encode writes them,
+ * and nothing else. For training a set, and for sizing a batch before committing to it. */
+int dc_huff_batch_set_select(dc_ctx *ctx, const uint8_t *d_in, const uint64_t *d_in_off, uint64_t count, int n_ary,
+                             const uint8_t *d_set, uint32_t K, uint8_t *d_tid, uint8_t *d_mode, uint32_t *d_bits,
+                             int32_t *d_status);
+int dc_huff_encode_batch_set(dc_ctx *ctx, const uint8_t *d_in, const uint64_t *d_in_off, uint64_t count,
+                             const uint8_t *d_set, uint32_t K, uint8_t *d_tid, const dc_hbatch *batch);
+int dc_huff_decode_batch_set(dc_ctx *ctx, const dc_hbatch *batch, const uint8_t *d_set, uint32_t K,
+                             const uint8_t *d_tid, uint8_t *d_out, const uint64_t *d_out_off, uint64_t out_cap);
+int dc_huff_decode_batch_set_scatter(dc_ctx *ctx, const dc_hbatch *batch, const uint8_t *d_set, uint32_t K,
+                                     const uint8_t *d_tid, uint8_t *d_out, const uint64_t *d_out_beg,
+                                     const uint64_t *d_out_end, uint64_t out_cap);
+/* byte ranges ("byte ranges of segments" above) of a table-set batch: test 6 is DC_E_STREAM for a
+ * mode-1 segment whose tid is >= K or whose record gives no code. A list sorted by tid pays one
+ * table build per record and workgroup. */
+int dc_huff_decode_batch_set_ranges(dc_ctx *ctx, const dc_hbatch *batch, const uint8_t *d_set, uint32_t K,
+                                    const uint8_t *d_tid, const uint64_t *d_seg_off, const uint64_t *d_seg,
+                                    const uint64_t *d_first, const uint64_t *d_count, const uint64_t *d_out_off,
+                                    uint64_t nranges, uint8_t *d_out, uint64_t out_cap, int32_t *d_rstatus);
+/* d_hist (u64[256 K]) is zeroed, then hist[k][s] = the number of bytes s in the segments with
+ * valid offsets and d_tid[i] == k; segments with bad offsets or d_tid[i] >= K are skipped. One
+ * launch, no host read. DC_E_ARG for K outside 1..DC_BATCH_SET_MAX or a NULL pointer. */
+int dc_huff_batch_set_hist(dc_ctx *ctx, const uint8_t *d_in, const uint64_t *d_in_off, uint64_t count,
+                           const uint8_t *d_tid, uint32_t K, uint64_t *d_hist);
 
 /* base64url text (6 bits per char, MSB-first) of bits [bit_base, bit_base+bits) */
 int dc_huff_base64url(dc_ctx *ctx, const uint32_t *d_words, uint64_t bit_base, uint64_t bits,

@@ -30,10 +30,23 @@ of bench.py (synth.device_text, seed 0xC2, n = 2, S = 64), one process:
           stored, the stored size with 256-byte and with 128-byte lens records, and the
           batch_lens_pack / batch_lens_unpack times. Every figure is the median of `--rounds`
           rounds with its (min, max): the spread a call shows against itself.
+  set     (only on request) a table set (encode_blocks(..., table_set=)) between the two: on
+          corpus (a), the C2 text, and on corpus (b), a mixed corpus of the same size in regions
+          of 16 MiB (enwik-like, english-like, log-like, zipf bytes, hex digits, uniform bytes, in
+          turn), both block sizes, four rows each: own tables, one shared table of the whole
+          corpus, and sets of K = 4 and K = 16 trained by Codec.batch_table_set (its wall time is
+          in the row). The four rows alternate inside every round. Per row: the whole encode and
+          the decode (HIP-event windows), the plan and pack kernels' own times (dc_ctx_timings, one
+          call a round), the payload bytes and the stored bytes (payload + u16 index + 5 B per
+          segment, plus 256 B of lens per segment, or the table's lengths once, or 1 B of tid per
+          segment and the K records once, 128 B each when they pack as nybbles); for a set, how
+          many coded segments chose each record and how many were stored. Then per corpus and
+          block size the set rows against the own-table and the shared-table rows.
 Every result is checked against the input before it is timed. One JSON line per result.
     timeout 900 python tools/batch_bench.py [--size BYTES] [--steps K] [--rounds R] [--only blocks,loop,shared]
     timeout 900 python tools/batch_bench.py --only ranges
     timeout 900 python tools/batch_bench.py --only limit
+    timeout 900 python tools/batch_bench.py --only set
 """
 import argparse
 import ctypes
@@ -300,6 +313,120 @@ if "limit" in a.only:
              ms={k: {s: round(statistics.median(v), 4) for s, v in d.items()} for k, d in stages.items()},
              min_max_ms={k: {s: (round(min(v), 4), round(max(v), 4)) for s, v in d.items()} for k, d in stages.items()})
         del encs, bufs, packed
+    del out
+
+if "set" in a.only.split(","):
+    REGION = 16 << 20
+
+    def mixed(n):
+        """Corpus (b): regions of REGION bytes of six kinds in turn, made on the device."""
+        nreg = (n + REGION - 1) // REGION
+        kinds = ("C2", "C1", "C5", "C4", "hex", "C3")
+        per = (nreg + len(kinds) - 1) // len(kinds)
+        out = torch.empty(nreg * REGION, dtype=torch.uint8, device=dev)
+        digits = torch.tensor(list(b"0123456789abcdef"), dtype=torch.uint8, device=dev)
+        for j, kind in enumerate(kinds):
+            if kind == "hex":
+                g = torch.Generator(device=dev).manual_seed(0xB6)
+                src = digits[torch.randint(0, 16, (per * REGION,), generator=g, device=dev)]
+            else:
+                src = synth.device_text(kind, per * REGION, seed=0xB0 + j, device=dev)
+            for r in range(j, nreg, len(kinds)):
+                out[r * REGION: (r + 1) * REGION] = src[(r // len(kinds)) * REGION: (r // len(kinds) + 1) * REGION]
+            del src
+        return out[:n].contiguous()
+
+    KINDS = ("own", "shared", "set4", "set16")
+    out = torch.empty(n, dtype=torch.uint8, device=dev)
+    for corpus, xc in (("a_C2_text", x), ("b_mixed", mixed(n))):
+        tab = c.batch_table(xc, n_ary=2)
+        lengths = c.table_get_lengths(tab)
+        for block in (65536, 4096):
+            count = (n + block - 1) // block
+            offsets = c._block_offsets(xc, block)
+            pb, sb = c.batch_bounds(n, count, S)
+            bufs = {k: (torch.empty(pb, dtype=torch.uint8, device=dev), torch.empty(sb, dtype=torch.int16, device=dev))
+                    for k in KINDS}
+            sets, train_ms = {}, {}
+            for k in (4, 16):
+                c.batch_table_set(xc[: 64 * block], offsets[:65] - offsets[:1], k)   # (allocations and first launches)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                sets[f"set{k}"] = c.batch_table_set(xc, offsets, k, n_ary=2, max_bits=12, iters=2)
+                torch.cuda.synchronize()
+                train_ms[f"set{k}"] = round((time.perf_counter() - t0) * 1e3, 2)
+
+            def encode(kind):
+                kw = {"table": tab} if kind == "shared" else {"table_set": sets[kind]} if kind in sets else {}
+                return c.encode_blocks(xc, block=block, n_ary=2, sync_syms=S, payload=bufs[kind][0], sync_len=bufs[kind][1], **kw)
+
+            encs, size, rows = {}, {}, {}
+            for kind in KINDS:
+                enc = encs[kind] = encode(kind)
+                assert c.batch_status() == 0
+                out.zero_()
+                c.decode_batch(enc, out=out, out_off=enc["offsets"])
+                assert c.batch_status() == 0 and torch.equal(out, xc), kind + ": batch round trip differs from the input"
+                pay, idx = int(enc["pay_off"][-1]), int(enc["sync_off"][-1])
+                row = {"what": "set_size", "corpus": corpus, "table": kind, "block": block, "count": count, "payload_bytes": pay,
+                       "sync_entries": idx, "huffman_segments": int(enc["mode"].sum()),
+                       "payload_bits_per_byte": round(8 * pay / n, 4)}
+                if kind == "own":
+                    c.batch_lens_pack(enc)
+                    rec = count * (128 if c.batch_status() == 0 else 256)
+                    size[kind] = pay + 2 * idx + count * 5 + rec
+                elif kind == "shared":
+                    rec = int(lengths.size)
+                    size[kind] = pay + 2 * idx + count * 5 + rec
+                else:
+                    K = sets[kind].shape[0]
+                    c.batch_lens_pack({"lens": sets[kind], "count": K})
+                    rec = K * (128 if c.batch_status() == 0 else 256)
+                    size[kind] = pay + 2 * idx + count * 6 + rec
+                    chose = torch.bincount(enc["tid"][enc["mode"] == 1].to(torch.int64), minlength=K)
+                    row.update(K=K, train_ms=train_ms[kind], coded_segments_per_record=chose.cpu().tolist(),
+                               stored_segments=int((enc["mode"] == 0).sum()))
+                row.update(record_bytes=rec, stored_bytes=size[kind])
+                rows[kind] = row
+                emit(**row)
+            fns = {}
+            for kind in KINDS:
+                fns["encode_" + kind] = lambda kind=kind: encode(kind)
+                fns["decode_" + kind] = lambda kind=kind: c.decode_batch(encs[kind], out=out, out_off=offsets)
+            for fn in fns.values():
+                fn()
+            torch.cuda.synchronize()
+            t = {k: [] for k in fns}
+            stages = {kind: {} for kind in KINDS}
+            for _ in range(a.rounds):
+                for k, fn in fns.items():
+                    t[k].append(ev_ms(fn, a.steps))
+                for kind in KINDS:   # the kernels' own times (events around each launch: slower end to end, so apart)
+                    c.timing(True)
+                    encode(kind)
+                    c.decode_batch(encs[kind], out=out, out_off=offsets)
+                    for name, ms in c.timings():   # hb_plan, hbs_plan, hbm_plan: "plan" in every row
+                        stages[kind].setdefault(name.split("_", 1)[1], []).append(ms)
+                    c.timing(False)
+            med = {k: round(statistics.median(v), 4) for k, v in t.items()}
+            emit(what="set_time", corpus=corpus, block=block, count=count, ms=med,
+                 min_max_ms={k: (round(min(v), 4), round(max(v), 4)) for k, v in t.items()})
+            emit(what="set_stages", corpus=corpus, block=block, count=count,
+                 ms={k: {s_: round(statistics.median(v), 4) for s_, v in d.items()} for k, d in stages.items()},
+                 min_max_ms={k: {s_: (round(min(v), 4), round(max(v), 4)) for s_, v in d.items()} for k, d in stages.items()})
+            for kind in ("set4", "set16"):   # the comparison: the set against the two modes it lies between
+                vs = {"what": "set_vs", "corpus": corpus, "block": block, "count": count, "table": kind}
+                for other in ("own", "shared"):
+                    vs[f"stored_bytes_over_{other}"] = round(size[kind] / size[other], 4)
+                    for op in ("encode", "decode"):
+                        vs[f"{op}_ms_over_{other}"] = round(med[f"{op}_{kind}"] / med[f"{op}_{other}"], 4)
+                vs.update(stored_bytes={k: size[k] for k in ("own", "shared", kind)},
+                          encode_ms={k: med["encode_" + k] for k in ("own", "shared", kind)},
+                          decode_ms={k: med["decode_" + k] for k in ("own", "shared", kind)},
+                          slower_than_own=[op for op in ("encode", "decode") if med[f"{op}_{kind}"] > med[f"{op}_own"]])
+                emit(**vs)
+            del encs, bufs, sets
+        del tab
     del out
 
 if "ranges" in a.only:
