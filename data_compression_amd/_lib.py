@@ -198,6 +198,7 @@ def _declare_core(L):
         "dc_huff_decompress_netstring": ([u8p, u64, u8p, u64, C.POINTER(u64)], i32),
         "dc_huff_netstring_info": ([u8p, u64, C.POINTER(u64)], i32),
         "dc_huff_container_info": ([u8p, u64, C.POINTER(u64), C.POINTER(i32), C.POINTER(u64)], i32),
+        "dc_huff_container_check": ([u8p, u64], i32),
         "dc_huff_range_span": ([u64, u32, C.POINTER(u64), u64, u64, u64, C.POINTER(u64)], i32),
         "dc_huff_decompress_range_host": ([u8p, u64, u64, u64, u8p, u64, C.POINTER(u64)], i32),
         "dc_nyb_compress_host": ([u8p, u64, i32, u8p, u64, C.POINTER(u64)], i32),

@@ -14,6 +14,9 @@
 #include "dc_gpu.h"
 #include "dc_host.h"
 #include "dc_range_span.h"
+#include "dc_container_check.h"
+
+static_assert(DCC_SYNC_MAX == DC_SYNC_MAX && DCC_MAX_DIGITS == DC_MAX_DIGITS, "dc_container_check.h restates dc_gpu.h");
 
 namespace {
 
@@ -59,6 +62,7 @@ int state(HostState **s)
 
 const uint32_t kMagic = 0x31484344u;   // "DCH1" little-endian
 const size_t kHeader = 288;
+static_assert(kMagic == DCC_MAGIC && kHeader == DCC_HEADER, "dc_container_check.h restates the DCH1 header");
 
 inline void put32(uint8_t *p, uint32_t v) { memcpy(p, &v, 4); }
 inline void put64(uint8_t *p, uint64_t v) { memcpy(p, &v, 8); }
@@ -199,15 +203,13 @@ int dc_huff_decompress_host(const uint8_t *in, uint64_t m, uint8_t *out, uint64_
 {
     if (!in || !out_len) return DC_E_ARG;
     if (m < 4 || get32(in) != kMagic) return dc_huff_decompress_netstring(in, m, out, cap, out_len);
-    uint64_t n = 0, bits = 0;
-    int nary = 0;
-    RC(dc_huff_container_info(in, m, &n, &nary, &bits));
-    const uint32_t S = get32(in + 24);
-    if (S < 16 || S > DC_SYNC_MAX || (S & (S - 1)) || nary < 2) return DC_E_STREAM;
-    const uint64_t ng = dc_huff_sync_groups(n, S), nc = dc_huff_sync_chunks(n, S);
-    const uint64_t ib = index_bytes(n, S);
-    const uint64_t nbytes = (bits + 7) / 8;
-    if (kHeader + ib + nbytes > m) return DC_E_STREAM;
+    // the header and the whole index are the file's: held to dc_container_check.h before any of
+    // them is uploaded (the decoder loads at the index's offsets unchecked)
+    dcc_dch1 hd;
+    if (dcc_dch1_check(in, m, &hd)) return DC_E_STREAM;
+    const uint64_t n = hd.n, bits = hd.bits, ng = hd.ng, nc = hd.nc, ib = hd.ib, nbytes = hd.nbytes;
+    const uint32_t S = hd.S;
+    const int nary = hd.n_ary;
     if (n > cap) return DC_E_CAPACITY;
     if (n && !out) return DC_E_ARG;
     HostState *s;
@@ -254,15 +256,11 @@ int dc_huff_decompress_range_host(const uint8_t *in, uint64_t m, uint64_t first,
 {
     if (!in || !out_len) return DC_E_ARG;
     if (m < 4 || get32(in) != kMagic) return DC_E_ARG;   // a netstring container: its index is base64url text
-    uint64_t n = 0, bits = 0;
-    int nary = 0;
-    RC(dc_huff_container_info(in, m, &n, &nary, &bits));
-    const uint32_t S = get32(in + 24);
-    if (S < 16 || S > DC_SYNC_MAX || (S & (S - 1)) || nary < 2) return DC_E_STREAM;
-    const uint64_t ng = dc_huff_sync_groups(n, S), nc = dc_huff_sync_chunks(n, S);
-    const uint64_t ib = index_bytes(n, S);
-    const uint64_t nbytes = (bits + 7) / 8;
-    if (kHeader + ib + nbytes > m) return DC_E_STREAM;
+    dcc_dch1 hd;
+    if (dcc_dch1_header(in, m, &hd)) return DC_E_STREAM;
+    const uint64_t n = hd.n, bits = hd.bits, ng = hd.ng, nc = hd.nc, ib = hd.ib;
+    const uint32_t S = hd.S;
+    const int nary = hd.n_ary;
     if (first > n || count > n - first) return DC_E_ARG;
     if (count > cap) return DC_E_CAPACITY;
     *out_len = 0;
@@ -279,7 +277,9 @@ int dc_huff_decompress_range_host(const uint8_t *in, uint64_t m, uint64_t first,
     uint64_t sp[4];
     RC(dc_huff_range_span(n, S, bases, bits, first, count, sp));
     const uint64_t g0 = sp[0], g1 = sp[1], b0 = sp[2], b1 = sp[3];
-    if (b0 > b1 || b1 > bits) return DC_E_STREAM;
+    // the index rule on the groups read (a range read stays sub-linear): the bytes checked here,
+    // in place, are the ones uploaded below, and b0 <= b1 <= bits follows
+    if (dcc_index_groups(n, S, in + kHeader, in + kHeader + ng * 8, bits, 0, g0, g1)) return DC_E_STREAM;
     HostState *s;
     RC(state(&s));
     dc_ctx *c = s->ctx;
@@ -471,9 +471,94 @@ bool ns_meta_get(const uint8_t *s, uint64_t len, const char *key, uint64_t *v)
 struct NsSeg {
     uint64_t nary = 0, syms = 0, bits = 0, S = 0, M = 258;
     bool have_meta = false, have_table = false;
-    int32_t lengths[DC_MAX_SYMS];
+    int32_t lengths[DC_MAX_SYMS] = {};
     uint64_t zchars = 0, ichars = 0;
+    uint64_t dpos = 0;              // where its symbols go in the output
+    std::vector<uint64_t> zr, ir;   // (offset, length) pairs of its Z / index text in the container
 };
+
+// What the host sees of a netstring container, in order: the raw blocks, the Huffman segments and
+// the decompressed size.
+struct NsPlan {
+    std::vector<uint64_t> raw;   // (src, len, dst) triples of raw blocks
+    std::vector<NsSeg> segs;
+    uint64_t n = 0;
+};
+
+// a finished Huffman segment joins the plan: its metadata must be whole and agree with the text
+// it came with (m: the container's bytes, which bound the index text)
+int ns_plan_close(NsSeg &seg, uint64_t m, NsPlan *pl)
+{
+    if (!seg.have_meta && !seg.zchars) return DC_OK;
+    if (!seg.have_meta || !seg.have_table || seg.nary < 2 || seg.nary > 256) return DC_E_STREAM;
+    if (!dcc_sync_ok(seg.S) || !dcc_bits_fit(seg.bits, seg.syms) || seg.zchars != dcc_ceil_div(seg.bits, 6))
+        return DC_E_STREAM;
+    const uint64_t ib = dcc_index_bytes(seg.syms, (uint32_t)seg.S);
+    if (ib > m || seg.ichars != dcc_ceil_div(ib * 8, 6)) return DC_E_STREAM;
+    seg.dpos = pl->n;
+    if (dcc_add(pl->n, seg.syms, &pl->n)) return DC_E_STREAM;
+    pl->segs.push_back(seg);
+    seg = NsSeg();
+    return DC_OK;
+}
+
+// Walk the blocks on the host (no device): block syntax, block types, each segment's metadata,
+// and the output size summed without wrap. DC_OK or DC_E_STREAM.
+int ns_plan(const uint8_t *in, uint64_t m, NsPlan *pl)
+{
+    NsSeg seg;
+    uint64_t p = 0;
+    NsBlock b;
+    bool bad = false;
+    while (ns_next(in, m, &p, &b, &bad)) {
+        const uint8_t *d = in + b.off;
+        switch (b.type) {
+        case '\n':   // raw pass-through (:2071-2076): the payload after the type bytes
+            RC(ns_plan_close(seg, m, pl));
+            pl->raw.push_back(b.off); pl->raw.push_back(b.len); pl->raw.push_back(pl->n);
+            if (dcc_add(pl->n, b.len, &pl->n)) return DC_E_STREAM;
+            break;
+        case '#':
+            if (b.len >= 4 && memcmp(d, "dc1 ", 4) == 0) {   // starts a Huffman segment
+                RC(ns_plan_close(seg, m, pl));
+                uint64_t v = 0;
+                seg.have_meta = ns_meta_get(d, b.len, "n", &seg.nary) && ns_meta_get(d, b.len, "syms", &seg.syms) &&
+                                ns_meta_get(d, b.len, "bits", &seg.bits) && ns_meta_get(d, b.len, "S", &seg.S);
+                if (ns_meta_get(d, b.len, "M", &v)) seg.M = v;
+                if (!seg.have_meta || seg.M >= DC_MAX_SYMS) return DC_E_STREAM;
+            } else if (b.len >= 6 && memcmp(d, "dcidx:", 6) == 0) {
+                seg.ir.push_back(b.off + 6); seg.ir.push_back(b.len - 6);
+                seg.ichars += b.len - 6;
+            }   // other metadata: skipped (:2077-2080)
+            break;
+        case 'X': {   // "<M>:" then one length character per symbol 0..M (:1710-1747)
+            char *e = nullptr;
+            char num[16] = {0};
+            memcpy(num, d, b.len < 15 ? b.len : 15);
+            const long Mx = strtol(num, &e, 10);
+            if (e == num || *e != ':' || Mx < 0 || Mx >= DC_MAX_SYMS) return DC_E_STREAM;
+            const uint64_t h0 = (uint64_t)(e - num) + 1;
+            if (b.len != h0 + (uint64_t)Mx + 1) return DC_E_STREAM;
+            for (long i = 0; i <= Mx; ++i) {
+                const char *q = strchr(kLenDigits, d[h0 + i]);
+                if (!q || !d[h0 + i]) return DC_E_STREAM;
+                seg.lengths[i] = (int32_t)(q - kLenDigits);
+            }
+            seg.M = (uint64_t)Mx;
+            seg.have_table = true;
+            break;
+        }
+        case 'Z':
+            seg.zr.push_back(b.off); seg.zr.push_back(b.len);
+            seg.zchars += b.len;
+            break;
+        default:
+            return DC_E_STREAM;   // unknown block type (:2067-2070)
+        }
+    }
+    if (bad) return DC_E_STREAM;
+    return ns_plan_close(seg, m, pl);
+}
 
 }  // namespace
 
@@ -581,10 +666,11 @@ int dc_huff_netstring_info(const uint8_t *in, uint64_t m, uint64_t *out_n)
     bool bad = false;
     while (ns_next(in, m, &p, &b, &bad)) {
         if (b.type != '\n' && b.type != '#' && b.type != 'X' && b.type != 'Z') return DC_E_STREAM;   // :2067-2070
-        if (b.type == '\n') tot += b.len;
-        else if (b.type == '#' && b.len >= 4 && memcmp(in + b.off, "dc1 ", 4) == 0 &&
-                 ns_meta_get(in + b.off, b.len, "syms", &v))
-            tot += v;
+        if (b.type == '\n') v = b.len;
+        else if (!(b.type == '#' && b.len >= 4 && memcmp(in + b.off, "dc1 ", 4) == 0 &&
+                   ns_meta_get(in + b.off, b.len, "syms", &v)))
+            continue;
+        if (dcc_add(tot, v, &tot)) return DC_E_STREAM;   // a size no buffer has: callers allocate from it
     }
     if (bad) return DC_E_STREAM;
     *out_n = tot;
@@ -594,8 +680,9 @@ int dc_huff_netstring_info(const uint8_t *in, uint64_t m, uint64_t *out_n)
 int dc_huff_decompress_netstring(const uint8_t *in, uint64_t m, uint8_t *out, uint64_t cap, uint64_t *out_len)
 {
     if (!in || !out_len) return DC_E_ARG;
-    uint64_t n = 0;
-    RC(dc_huff_netstring_info(in, m, &n));
+    NsPlan pl;
+    RC(ns_plan(in, m, &pl));   // all the host can see of the container, before the first device call
+    const uint64_t n = pl.n;
     if (n > cap) return DC_E_CAPACITY;
     if (n && !out) return DC_E_ARG;
     *out_len = 0;
@@ -608,10 +695,7 @@ int dc_huff_decompress_netstring(const uint8_t *in, uint64_t m, uint8_t *out, ui
     RC(dc_host_upload(in, m, &d_src));
     RC(s->out.need(n + 64));
     uint8_t *d_dst = (uint8_t *)s->out.p;
-    std::vector<uint64_t> raw;            // (src, len, dst) triples of raw blocks
-    uint64_t dpos = 0;                    // output position
-    NsSeg seg;
-    std::vector<uint64_t> zr, ir;         // text ranges of the current segment's Z / index blocks
+    std::vector<uint8_t> h_index;
     auto gather = [&](const std::vector<uint64_t> &r, uint8_t *dst) -> int {
         const uint64_t k = r.size() / 3;
         if (!k) return DC_OK;
@@ -622,14 +706,11 @@ int dc_huff_decompress_netstring(const uint8_t *in, uint64_t m, uint8_t *out, ui
         if (hipGetLastError() != hipSuccess) return DC_E_HIP;
         return dc_ctx_sync(c);
     };
-    auto flush = [&]() -> int {   // decode the finished Huffman segment into d_dst + dpos
-        if (!seg.have_meta && !seg.zchars) return DC_OK;
-        if (!seg.have_meta || !seg.have_table || seg.nary < 2 || seg.nary > 256) return DC_E_STREAM;
+    auto decode = [&](const NsSeg &seg) -> int {   // one Huffman segment of the plan into d_dst + seg.dpos
         const uint32_t S = (uint32_t)seg.S;
-        if (S < 16 || S > DC_SYNC_MAX || (S & (S - 1)) || seg.zchars != (seg.bits + 5) / 6) return DC_E_STREAM;
+        const std::vector<uint64_t> &ir = seg.ir, &zr = seg.zr;
         const uint64_t ng = dc_huff_sync_groups(seg.syms, S), nc = dc_huff_sync_chunks(seg.syms, S);
         const uint64_t ib = ng * 8 + nc * 2;
-        if (seg.ichars != (ib * 8 + 5) / 6 || dpos + seg.syms > n) return DC_E_STREAM;
         // index and data text -> contiguous device text -> bits
         RC(s->aux.need(seg.ichars + seg.zchars + 64));
         uint8_t *d_it = (uint8_t *)s->aux.p, *d_zt = d_it + seg.ichars;
@@ -644,6 +725,11 @@ int dc_huff_decompress_netstring(const uint8_t *in, uint64_t m, uint8_t *out, ui
         RC(dc_memset(c, s->in2.p, 0, words * 4 + 64));
         RC(dc_huff_text_parse(c, (const char *)d_it, seg.ichars, DC_TEXT_BASE64URL, 2, ib * 8, (uint32_t *)s->sync.p));
         RC(dc_huff_text_parse_status(c));
+        // the index is the file's text, parsed on the device: read its ib bytes back (2.125 / S bytes
+        // per symbol) and hold them to the index rule before the decoder loads at its offsets
+        h_index.resize(ib);
+        if (ib) RC(dc_memcpy_d2h(c, h_index.data(), s->sync.p, ib));
+        if (dcc_index(seg.syms, S, h_index.data(), h_index.data() + ng * 8, seg.bits, 0)) return DC_E_STREAM;
         RC(dc_huff_text_parse(c, (const char *)d_zt, seg.zchars, DC_TEXT_BASE64URL, 2, seg.bits, (uint32_t *)s->in2.p));
         RC(dc_huff_text_parse_status(c));
         const int M = (int)seg.M;
@@ -655,7 +741,7 @@ int dc_huff_decompress_netstring(const uint8_t *in, uint64_t m, uint8_t *out, ui
         int32_t mb = 0;
         if (dc_huff_table_status(c, d_tab, &mb) != DC_OK || mb > 32) return DC_E_STREAM;
         // decode into a 16-B aligned scratch when the segment does not start aligned
-        uint8_t *dst = d_dst + dpos;
+        uint8_t *dst = d_dst + seg.dpos;
         const bool aligned = (((uintptr_t)dst) & 15) == 0;
         if (!aligned) RC(s->aux2.need(seg.syms + 64));
         uint64_t *d_base = (uint64_t *)s->sync.p;
@@ -664,68 +750,24 @@ int dc_huff_decompress_netstring(const uint8_t *in, uint64_t m, uint8_t *out, ui
         RC(dc_huff_decode_status(c));
         if (!aligned && hipMemcpyAsync(dst, s->aux2.p, seg.syms, hipMemcpyDeviceToDevice, st) != hipSuccess)
             return DC_E_HIP;
-        dpos += seg.syms;
-        seg = NsSeg();
-        zr.clear();
-        ir.clear();
         return DC_OK;
     };
-    uint64_t p = 0;
-    NsBlock b;
-    bool bad = false;
-    while (ns_next(in, m, &p, &b, &bad)) {
-        const uint8_t *d = in + b.off;
-        switch (b.type) {
-        case '\n':   // raw pass-through (:2071-2076): the payload after the type bytes
-            RC(flush());
-            raw.push_back(b.off); raw.push_back(b.len); raw.push_back(dpos);
-            dpos += b.len;
-            break;
-        case '#':
-            if (b.len >= 4 && memcmp(d, "dc1 ", 4) == 0) {   // starts a Huffman segment
-                RC(flush());
-                uint64_t v = 0;
-                seg.have_meta = ns_meta_get(d, b.len, "n", &seg.nary) && ns_meta_get(d, b.len, "syms", &seg.syms) &&
-                                ns_meta_get(d, b.len, "bits", &seg.bits) && ns_meta_get(d, b.len, "S", &seg.S);
-                if (ns_meta_get(d, b.len, "M", &v)) seg.M = v;
-                if (!seg.have_meta || seg.M >= DC_MAX_SYMS) return DC_E_STREAM;
-            } else if (b.len >= 6 && memcmp(d, "dcidx:", 6) == 0) {
-                ir.push_back(b.off + 6); ir.push_back(b.len - 6);
-                seg.ichars += b.len - 6;
-            }   // other metadata: skipped (:2077-2080)
-            break;
-        case 'X': {   // "<M>:" then one length character per symbol 0..M (:1710-1747)
-            char *e = nullptr;
-            char num[16] = {0};
-            memcpy(num, d, b.len < 15 ? b.len : 15);
-            const long Mx = strtol(num, &e, 10);
-            if (e == num || *e != ':' || Mx < 0 || Mx >= DC_MAX_SYMS) return DC_E_STREAM;
-            const uint64_t h0 = (uint64_t)(e - num) + 1;
-            if (b.len != h0 + (uint64_t)Mx + 1) return DC_E_STREAM;
-            for (long i = 0; i <= Mx; ++i) {
-                const char *q = strchr(kLenDigits, d[h0 + i]);
-                if (!q || !d[h0 + i]) return DC_E_STREAM;
-                seg.lengths[i] = (int32_t)(q - kLenDigits);
-            }
-            seg.M = (uint64_t)Mx;
-            seg.have_table = true;
-            break;
-        }
-        case 'Z':
-            zr.push_back(b.off); zr.push_back(b.len);
-            seg.zchars += b.len;
-            break;
-        default:
-            return DC_E_STREAM;   // unknown block type (:2067-2070)
-        }
-    }
-    if (bad) return DC_E_STREAM;
-    RC(flush());
-    if (dpos != n) return DC_E_STREAM;
-    RC(gather(raw, d_dst));
+    for (const NsSeg &seg : pl.segs) RC(decode(seg));
+    RC(gather(pl.raw, d_dst));
     RC(dc_memcpy_d2h(c, out, d_dst, n));
     *out_len = n;
     return DC_OK;
+}
+
+int dc_huff_container_check(const uint8_t *in, uint64_t m)
+{
+    if (!in) return DC_E_STREAM;
+    if (m >= 4 && get32(in) == kMagic) {
+        dcc_dch1 hd;
+        return dcc_dch1_check(in, m, &hd) ? DC_E_STREAM : DC_OK;
+    }
+    NsPlan pl;
+    return ns_plan(in, m, &pl);
 }
 
 // ---- host-buffer nybble / small wrappers (byte arrays, explicit lengths) --------------

@@ -40,6 +40,17 @@ int dc_huff_compress_host(const uint8_t *in, uint64_t n, int n_ary, const int32_
 int dc_huff_decompress_host(const uint8_t *in, uint64_t m, uint8_t *out, uint64_t cap,
                             uint64_t *out_len);
 int dc_huff_container_info(const uint8_t *in, uint64_t m, uint64_t *n, int *n_ary, uint64_t *bits);
+/* Is a container that was read from a file safe to decode? Host arithmetic only: no device, no
+ * context. DC_OK or DC_E_STREAM. "DCH1": the header rule (version 1, n_ary 2..16, w its digit
+ * width, flags 0, a valid sync_syms, every length <= DC_MAX_DIGITS, bits <= 32 n, header + index +
+ * payload <= m without wrap) and the index rule (bases[0] == 0, each base + its group's lengths ==
+ * the next base, the last == bits, a chunk of k symbols <= 32 k bits), so that every chunk starts
+ * inside the payload. Anything else is read as netstrings: block syntax and types, each segment's
+ * metadata against its text, the output size without wrap (its index is text that only the device
+ * parses: dc_huff_decompress_netstring applies the index rule itself). Both decompress calls and
+ * the range read run these checks before their first device call (the range read on the groups it
+ * uploads). */
+int dc_huff_container_check(const uint8_t *in, uint64_t m);
 /* Range reads by the sync index.
  * dc_huff_range_span: pure host arithmetic (no device): the part of a stream that symbols
  * [first, first+count) need. out[0] = first group g0, out[1] = last group g1, out[2] = first
