@@ -6353,6 +6353,7 @@ struct dc_ctx {
     uint32_t opt_decode_variant;  // fast decoder: 0 one code per lookup (k_huff_decode8), 1 up to 3 (k_huff_decode9)
     uint32_t opt_adec_v1;         // adaptive nybble decode: 0 control words + k_nyb_resolve_c, 1 = the one-pass
                                   // k_nyb_adec, 2 = r2's k_nyb_resolve, 3 = k_nyb_resolve_s (A/B)
+    uint32_t opt_adec_seg;        // adaptive nybble decode: tokens per launch of k_nyb_resolve_c (0: ADEC_SEG)
     // timing
     int timing, nev;
     hipEvent_t ev0[DC_MAX_EVENTS], ev1[DC_MAX_EVENTS];
@@ -6574,6 +6575,7 @@ int dc_ctx_set_option(dc_ctx *c, int option, int64_t value)
         {DC_OPT_PACK_BLOCK, &dc_ctx::opt_pack_block, 7, true},           // 2/3: k_huff_pack_w
         {DC_OPT_NYB_WTILE_OFF, &dc_ctx::opt_nyb_wtile_off, 1, false},
         {DC_OPT_BATCH_GRID, &dc_ctx::opt_batch_grid, 65536, false},
+        {DC_OPT_NYB_ADEC_SEG, &dc_ctx::opt_adec_seg, 16 << 20, false},   // 0 = ADEC_SEG, the largest value
     };
     for (const auto &o : opts) {
         if (o.id != option) continue;
@@ -7984,15 +7986,17 @@ static int mtf_run(dc_ctx *c, const uint8_t *d_in, uint64_t len, const MtfSum *h
 }
 
 // The adaptive decode's resolve (k_nyb_resolve_c) over the tokens in out[1, n), in segments
-// of ADEC_SEG tokens (a control dword each).
+// of ADEC_SEG tokens (a control dword each), or of DC_OPT_NYB_ADEC_SEG.
 #define ADEC_SEG (16ull << 20)
+static_assert(ADEC_SEG == (16 << 20), "the largest DC_OPT_NYB_ADEC_SEG (dc_ctx_set_option)");
 static int adec_fast(dc_ctx *c, uint8_t *d_out, uint64_t n)
 {
-    const uint64_t seg = std::min<uint64_t>(n - 1, ADEC_SEG);
+    const uint64_t step = c->opt_adec_seg ? c->opt_adec_seg : ADEC_SEG;
+    const uint64_t seg = std::min<uint64_t>(n - 1, step);
     if (ensure(c->ws.actl, (seg + 64) * sizeof(uint32_t))) return DC_E_HIP;
     if (!c->d_astate && hipMalloc(&c->d_astate, 64 * sizeof(uint32_t)) != hipSuccess) return DC_E_HIP;
-    for (uint64_t k0 = 1; k0 < n; k0 += ADEC_SEG) {
-        const uint64_t k1 = std::min<uint64_t>(k0 + ADEC_SEG, n);
+    for (uint64_t k0 = 1; k0 < n; k0 += step) {
+        const uint64_t k1 = std::min<uint64_t>(k0 + step, n);
         const uint64_t grid = std::min<uint64_t>((k1 - k0 + 255) / 256, 8192);
         LAUNCH(c, "nyb_adec_ctl", k_nyb_adec_ctl, grid, 256, (const uint8_t *)d_out, k0, k1, n, c->ws.actl.get());
         LAUNCH(c, "nyb_resolve", k_nyb_resolve_c, 1, 64, d_out, k0, k1, (const uint32_t *)c->ws.actl, c->d_astate,

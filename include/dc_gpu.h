@@ -148,9 +148,14 @@ enum {
     DC_OPT_NYB_WTILE_OFF = 9,     /* 1: the static nybble encode and the nybble decode write each
                                      4096-element tile with a workgroup (k_fsm_write) instead of a
                                      wave (k_nyb_enc_wtile / k_nyb_dec_wtile) */
-    DC_OPT_BATCH_GRID = 10        /* batch codec: workgroups of its persistent kernels, 0 = what a
+    DC_OPT_BATCH_GRID = 10,       /* batch codec: workgroups of its persistent kernels, 0 = what a
                                      256-CU device holds at once (768 plan, 512 pack / decode; the
                                      shared-table mode: 1024 plan, 512 pack / decode) */
+    DC_OPT_NYB_ADEC_SEG = 11      /* adaptive nybble decode (dc_nyb_decompress, modify = 1): tokens
+                                     per launch of the resolve (k_nyb_resolve_c), 0 = the default
+                                     of 16 Mi, which is also the largest value; the lists and the
+                                     previous byte pass from one launch to the next in device
+                                     memory. The output does not depend on it. */
 };
 int dc_ctx_set_option(dc_ctx *ctx, int option, int64_t value);
 const char *dc_version(void);

@@ -211,8 +211,8 @@ def test_nybble_256mib_vs_oracle(torch_cuda, modify):
     assert comp.numel() == len(want)
     assert np.array_equal(comp.cpu().numpy(), np.frombuffer(want, np.uint8))
     del want
-    if modify:   # the sequential resolve runs ~12 MB/s: its 256 MiB would take ~20 s, check 16 MiB
-        x16 = x[: 16 << 20]
+    if modify:   # the sequential resolve runs ~12 MB/s: its 256 MiB would take ~20 s, check 16 MiB and 200
+        x16 = x[: (16 << 20) + 200]   # bytes more: the resolve's second segment (adec_fast, 16 Mi tokens each)
         comp16 = c.nyb_compress(x16, True)
         y = c.nyb_decompress(comp16, True)
         assert torch.equal(y, x16)

@@ -861,7 +861,7 @@ def synth_text(n, seed):
 @pytest.mark.parametrize("v1", [0, 1, 3])
 def test_nybble_adaptive_decode_edges(torch_cuda, codec, v1):
     """Adaptive decode (tokens by the static transducer, then the resolve in place: 0 = control
-    words + k_nyb_resolve_c + the re-encode check, 3 = the exact k_nyb_resolve_s, 1 = the
+    words + k_nyb_resolve_c, which searches every literal, 3 = the plain-code k_nyb_resolve_s, 1 = the
     one-pass k_nyb_adec): every output size 1..200 and block-boundary sizes, output buffers at
     every offset mod 64 (the resolve kernels' first and last blocks), against the reference
     restatement."""
