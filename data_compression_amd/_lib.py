@@ -34,6 +34,25 @@ class HBatch(C.Structure):
                 ("d_sync_len", vp), ("sync_cap", u64), ("d_status", vp)]
 
 
+class HBlobInfo(C.Structure):
+    """dc_hblob_info (dc_gpu.h "container DCHB"): the header's fields, the section offsets and
+    the layout of open's workspace."""
+    _fields_ = [(f, u32) for f in ("version", "kind", "flags", "K")] + [("n_ary", C.c_int32), ("sync_syms", u32)] + \
+               [(f, u64) for f in ("count", "total_bytes", "sync_total", "pay_total", "blob_bytes", "len_off", "bits_off",
+                                   "mode_off", "tid_off", "crc_off", "rec_off", "rec_bytes", "payload_off", "sync_off",
+                                   "work_bytes", "w_items", "w_pay_off", "w_sync_off", "w_seg_off", "w_status",
+                                   "w_cstatus", "w_lens", "w_lengths", "w_table")]
+
+    def as_dict(self):
+        return {f: int(getattr(self, f)) for f, _ in self._fields_}
+
+
+class HBlobView(C.Structure):
+    """dc_hblob_view: the batch of an opened container and what its decode calls take."""
+    _fields_ = [("batch", HBatch), ("d_seg_off", vp), ("d_cstatus", vp), ("d_tid", vp), ("d_crc", vp), ("d_set", vp),
+                ("K", u32), ("d_table", vp), ("total_bytes", u64)]
+
+
 class DcError(RuntimeError):
     NAMES = {-1: "DC_E_ARG", -2: "DC_E_HIP", -3: "DC_E_CODE_TOO_LONG", -4: "DC_E_NOCODE",
              -5: "DC_E_STATE", -6: "DC_E_CAPACITY", -7: "DC_E_STREAM", -8: "DC_E_FALLBACK",
@@ -152,6 +171,12 @@ def _declare_core(L):
         "dc_huff_decode_batch_set_scatter": ([vp, C.POINTER(HBatch), P, u32, P, P, P, P, u64], i32),
         "dc_huff_decode_batch_set_ranges": ([vp, C.POINTER(HBatch), P, u32, P, P, P, P, P, P, u64, P, u64, P], i32),
         "dc_huff_batch_set_hist": ([vp, P, P, u64, P, u32, P], i32),
+        "dc_huff_batch_blob_bound": ([u64, u64, u32, i32, i32, u32], u64),
+        "dc_huff_batch_blob_layout": ([u64, i32, i32, u32, C.POINTER(HBlobInfo)], i32),
+        "dc_huff_batch_blob_info": ([P, u64, C.POINTER(HBlobInfo)], i32),
+        "dc_huff_batch_blob_check": ([P, u64], i32),
+        "dc_huff_batch_seal": ([vp, C.POINTER(HBatch), P, i32, i32, P, u32, P, P, P, u64, P, P], i32),
+        "dc_huff_batch_open": ([vp, P, u64, C.POINTER(HBlobInfo), P, u64, C.POINTER(HBlobView)], i32),
         "dc_huff_decode_redo_count": ([vp, C.POINTER(u64)], i32),
         "dc_huff_base64url": ([vp, P, u64, u64, P], i32),
         "dc_huff_text_bits": ([i32, i32], i32),
@@ -201,6 +226,9 @@ def _declare_core(L):
         "dc_huff_container_check": ([u8p, u64], i32),
         "dc_huff_range_span": ([u64, u32, C.POINTER(u64), u64, u64, u64, C.POINTER(u64)], i32),
         "dc_huff_decompress_range_host": ([u8p, u64, u64, u64, u8p, u64, C.POINTER(u64)], i32),
+        "dc_huff_batch_compress_host": ([u8p, C.POINTER(u64), u64, i32, u32, i32, i32, i32, u8p, u32, u8p, u64,
+                                         C.POINTER(u64)], i32),
+        "dc_huff_batch_decompress_host": ([u8p, u64, u8p, u64, C.POINTER(u64), C.POINTER(u64)], i32),
         "dc_nyb_compress_host": ([u8p, u64, i32, u8p, u64, C.POINTER(u64)], i32),
         "dc_nyb_decompress_host": ([u8p, u64, i32, u8p, u64, C.POINTER(u64)], i32),
         "dc_small_compress_host": ([u8p, u64, u8p, u64, C.POINTER(u64)], i32),

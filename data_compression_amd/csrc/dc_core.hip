@@ -24,6 +24,7 @@
 #include "dc_batch_set.h"
 #include "dc_huff_limit.h"
 #include "dc_crc32.h"
+#include "dc_batch_blob.h"
 
 #define DC_VERSION "dc-mi355x 0.1 (gfx950)"
 #define DC_SYNC_GROUP 64
@@ -6269,6 +6270,7 @@ __global__ __launch_bounds__(256) void k_copy_probe(const uint4 *__restrict__ sr
 #include "dc_nyb_batch_kernels.inc"
 #include "dc_small_batch_kernels.inc"
 #include "dc_crc_kernels.inc"
+#include "dc_batch_blob_kernels.inc"
 
 #ifdef DC_AB_KERNELS
 #include "dc_ab_kernels.inc"
@@ -8281,6 +8283,205 @@ int dc_crc32_verify_batch(dc_ctx *c, const uint8_t *d_in, uint64_t in_cap, const
     const uint64_t grid = hbatch_grid(c, (count + CRC_WAVES - 1) / CRC_WAVES, 2048);
     LAUNCH(c, "crc_verify", k_crc_batch<true>, grid, CRC_THREADS, d_in, in_cap, d_beg, d_end, count, d_expect,
            (uint32_t *)nullptr, d_status, first, (const uint32_t *)c->d_crct);
+    return DC_OK;
+}
+
+// the copy probe's grid: a workgroup per 4 KiB, grid-stride past 2^31 - 1 workgroups
+static uint64_t hbb_move_grid(uint64_t bytes)
+{
+    const uint64_t wgs = (bytes / 16 + 255) / 256;
+    return wgs < 1 ? 1 : wgs < 0x7fffffffull ? wgs : 0x7fffffffull;
+}
+// ---- the "DCHB" container of a Huffman batch (dc_batch_blob.h, dc_batch_blob_kernels.inc) ------
+static_assert(sizeof(dc_hblob_info) == sizeof(dc_bb_info), "dc_hblob_info is dc_bb_info");
+#define HBB_SAME(f) static_assert(offsetof(dc_hblob_info, f) == offsetof(dc_bb_info, f), "dc_hblob_info is dc_bb_info: " #f)
+HBB_SAME(version); HBB_SAME(kind); HBB_SAME(flags); HBB_SAME(K); HBB_SAME(n_ary); HBB_SAME(sync_syms); HBB_SAME(count);
+HBB_SAME(total_bytes); HBB_SAME(sync_total); HBB_SAME(pay_total); HBB_SAME(blob_bytes); HBB_SAME(len_off); HBB_SAME(bits_off);
+HBB_SAME(mode_off); HBB_SAME(tid_off); HBB_SAME(crc_off); HBB_SAME(rec_off); HBB_SAME(rec_bytes); HBB_SAME(payload_off);
+HBB_SAME(sync_off); HBB_SAME(work_bytes); HBB_SAME(w_items); HBB_SAME(w_pay_off); HBB_SAME(w_sync_off); HBB_SAME(w_seg_off);
+HBB_SAME(w_status); HBB_SAME(w_cstatus); HBB_SAME(w_lens); HBB_SAME(w_lengths); HBB_SAME(w_table);
+#undef HBB_SAME
+
+uint64_t dc_huff_batch_blob_bound(uint64_t total_bytes, uint64_t count, uint32_t S, int kind, int flags, uint32_t K)
+{
+    if (kind < 0 || flags < 0) return 0;
+    return dc_bb_bound(total_bytes, count, S, (uint32_t)kind, (uint32_t)flags, K);
+}
+
+int dc_huff_batch_blob_layout(uint64_t count, int kind, int flags, uint32_t K, dc_hblob_info *info)
+{
+    dc_bb_info I;
+    memset(&I, 0, sizeof(I));
+    if (!info || kind < 0 || flags < 0 || dc_bb_layout(count, (uint32_t)kind, (uint32_t)flags, K, &I)) return DC_E_ARG;
+    dc_bb_work(&I, sizeof(dc_dtable));
+    memcpy(info, &I, sizeof(I));
+    return DC_OK;
+}
+
+int dc_huff_batch_blob_info(const uint8_t *header64, uint64_t m, dc_hblob_info *info)
+{
+    dc_bb_info I;
+    memset(&I, 0, sizeof(I));
+    if (!header64 || !info) return DC_E_ARG;
+    if (dc_bb_header(header64, m, sizeof(dc_dtable), &I)) return DC_E_STREAM;
+    memcpy(info, &I, sizeof(I));
+    return DC_OK;
+}
+
+int dc_huff_batch_blob_check(const uint8_t *blob, uint64_t m)
+{
+    dc_bb_info I;
+    memset(&I, 0, sizeof(I));
+    if (!blob) return DC_E_ARG;
+    return dc_bb_check(blob, m, sizeof(dc_dtable), &I) ? DC_E_STREAM : DC_OK;
+}
+
+// [a, a + na) and [b, b + nb) share a byte
+static bool hbb_overlap(const void *a, uint64_t na, const void *b, uint64_t nb)
+{
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return a && b && na && nb && x < y + nb && y < x + na;
+}
+
+int dc_huff_batch_seal(dc_ctx *c, const dc_hbatch *b, const uint64_t *d_in_off, int kind, int flags, const void *tables,
+                       uint32_t K, const uint8_t *d_tid, const uint32_t *d_crc, uint8_t *d_blob, uint64_t blob_cap,
+                       uint64_t *d_info, int32_t *d_status)
+{
+    if (kind < 0 || flags < 0) return DC_E_ARG;
+    if (const int r = hbatch_args(c, b, kind <= (int)DC_BB_KIND_OWN4)) return r;
+    HbbSeal Z;
+    memset(&Z, 0, sizeof(Z));
+    const uint64_t n = b->count;
+    if (dc_bb_layout(n, (uint32_t)kind, (uint32_t)flags, K, &Z.I)) return DC_E_ARG;
+    if (!d_info || (blob_cap && !d_blob) || ((uintptr_t)d_blob & 15)) return DC_E_ARG;
+    if (kind >= (int)DC_BB_KIND_SHARED && !tables) return DC_E_ARG;
+    if (kind == (int)DC_BB_KIND_SET && ((uintptr_t)tables & 15)) return DC_E_ARG;
+    if (n && (!d_in_off || !d_status || (kind == (int)DC_BB_KIND_SET && !d_tid) || ((flags & DC_BB_FLAG_CRC) && !d_crc)))
+        return DC_E_ARG;
+    const bool in_place = b->d_payload && b->d_payload == d_blob + Z.I.payload_off;
+    if (hbb_overlap(d_blob, blob_cap, b->d_sync_len, 2 * b->sync_cap) || hbb_overlap(d_blob, blob_cap, b->d_mode, n) ||
+        hbb_overlap(d_blob, blob_cap, b->d_bits, 4 * n) || hbb_overlap(d_blob, blob_cap, b->d_pay_off, 8 * (n + 1)) ||
+        hbb_overlap(d_blob, blob_cap, b->d_sync_off, 8 * (n + 1)) || hbb_overlap(d_blob, blob_cap, b->d_status, 4 * n) ||
+        (kind <= (int)DC_BB_KIND_OWN4 && hbb_overlap(d_blob, blob_cap, b->d_lens, 256 * n)) ||
+        (!in_place && hbb_overlap(d_blob, blob_cap, b->d_payload, b->payload_cap)) ||
+        hbb_overlap(d_blob, blob_cap, d_info, 16) || hbb_overlap(d_blob, blob_cap, d_status, 4 * n) ||
+        hbb_overlap(d_blob, blob_cap, d_in_off, 8 * (n + 1)) || hbb_overlap(d_blob, blob_cap, d_tid, n) ||
+        hbb_overlap(d_blob, blob_cap, d_crc, 4 * n) ||
+        hbb_overlap(d_blob, blob_cap, tables, kind == (int)DC_BB_KIND_SHARED ? sizeof(dc_dtable) : 256ull * K))
+        return DC_E_ARG;
+    unsigned long long *first;
+    if (const int r = hbatch_begin(c, 1, &first)) return r;
+    Z.blob = d_blob;
+    Z.blob_cap = blob_cap;
+    Z.n_ary = (uint32_t)b->n_ary;
+    Z.S = b->sync_syms;
+    Z.pay_off = b->d_pay_off;
+    Z.sync_off = b->d_sync_off;
+    Z.pay_cap = b->payload_cap;
+    Z.sync_cap = b->sync_cap;
+    Z.info = d_info;
+    Z.total = first + 2;   // (ws.hb holds four words after hbatch_begin(c, 1))
+    Z.dir = Z.I.payload_off <= blob_cap;   // sections 1 to 6 are the host's to place: all of them, or none
+    HIPCHK(hipMemsetAsync(d_info, 0, 2 * sizeof(uint64_t), c->stream));
+    HIPCHK(hipMemsetAsync(Z.total, 0, sizeof(uint64_t), c->stream));
+    if (n && Z.dir) {
+        LAUNCH(c, "hbb_dir", k_hbb_dir, hbatch_grid(c, (n + HB_THREADS - 1) / HB_THREADS, 2048), HB_THREADS, Z, d_in_off,
+               (const uint8_t *)b->d_mode, (const uint32_t *)b->d_bits, (const int32_t *)b->d_status, d_tid, d_crc, d_status,
+               first);
+        const uint64_t gl = hbatch_grid(c, (n + HBL_RECS - 1) / HBL_RECS, 2048);
+        if (kind == (int)DC_BB_KIND_OWN)
+            LAUNCH(c, "hbb_lens", k_hbb_lens<false>, gl, HB_THREADS, (const uint8_t *)b->d_lens, n, (const int32_t *)b->d_status,
+                   d_blob + Z.I.rec_off, d_status, first);
+        if (kind == (int)DC_BB_KIND_OWN4)
+            LAUNCH(c, "hbb_lens4", k_hbb_lens<true>, gl, HB_THREADS, (const uint8_t *)b->d_lens, n, (const int32_t *)b->d_status,
+                   d_blob + Z.I.rec_off, d_status, first);
+    }
+    if (Z.dir) {
+        if (kind == (int)DC_BB_KIND_SHARED)
+            LAUNCH(c, "hbb_table_rec", k_hbb_table_rec, 1, HB_THREADS, (const dc_dtable *)tables, (int)b->n_ary,
+                   d_blob + Z.I.rec_off, d_info);
+        if (kind == (int)DC_BB_KIND_SET)
+            LAUNCH(c, "hbb_records", k_hbb_move<0>, hbb_move_grid(Z.I.rec_bytes), 256, Z, (const uint8_t *)tables, Z.I.rec_off,
+                   Z.I.rec_bytes);
+    }
+    if (n && Z.dir) {   // the two sections whose length the device knows, on grids sized by the batch's caps
+        if (!in_place && b->payload_cap)
+            LAUNCH(c, "hbb_payload", k_hbb_move<1>, hbb_move_grid(b->payload_cap), 256, Z, (const uint8_t *)b->d_payload, 0ull, 0ull);
+        if (b->sync_cap)
+            LAUNCH(c, "hbb_sync", k_hbb_move<2>, hbb_move_grid(2 * b->sync_cap), 256, Z, (const uint8_t *)b->d_sync_len, 0ull, 0ull);
+    }
+    LAUNCH(c, "hbb_header", k_hbb_header, 1, 64, Z);
+    return DC_OK;
+}
+
+int dc_huff_batch_open(dc_ctx *c, const uint8_t *d_blob, uint64_t m, const dc_hblob_info *info, void *d_work,
+                       uint64_t work_bytes, dc_hblob_view *view)
+{
+    if (!c || !d_blob || !info || !view || ((uintptr_t)d_blob & 15)) return DC_E_ARG;
+    dc_bb_info I, J;
+    memcpy(&I, info, sizeof(I));
+    memset(&J, 0, sizeof(J));
+    // the caps a decode is held to are section sizes checked here, whatever filled *info
+    uint64_t so, bb;
+    if (I.n_ary < 2 || I.n_ary > 256 || !dc_bb_sync_ok(I.sync_syms) || dc_bb_layout(I.count, I.kind, I.flags, I.K, &J) ||
+        J.len_off != I.len_off || J.bits_off != I.bits_off || J.mode_off != I.mode_off || J.tid_off != I.tid_off ||
+        J.crc_off != I.crc_off || J.rec_off != I.rec_off || J.rec_bytes != I.rec_bytes || J.payload_off != I.payload_off ||
+        dc_bb_tail(I.payload_off, I.pay_total, I.sync_total, &so, &bb) || so != I.sync_off || bb != I.blob_bytes || bb > m)
+        return DC_E_ARG;
+    J = I;
+    dc_bb_work(&J, sizeof(dc_dtable));
+    if (work_bytes < J.work_bytes || !d_work || ((uintptr_t)d_work & (DC_BB_WORK_ALIGN - 1))) return DC_E_ARG;
+    if (hbb_overlap(d_blob, m, d_work, work_bytes)) return DC_E_ARG;
+    I = J;
+    uint8_t *const w = (uint8_t *)d_work;
+    const uint64_t n = I.count;
+    uint64_t *const items = (uint64_t *)(w + I.w_items);
+    memset(view, 0, sizeof(*view));
+    dc_hbatch &b = view->batch;
+    b.count = n;
+    b.n_ary = I.n_ary;
+    b.sync_syms = I.sync_syms;
+    b.d_lens = I.kind == DC_BB_KIND_OWN ? const_cast<uint8_t *>(d_blob) + I.rec_off : I.kind == DC_BB_KIND_OWN4 ? w + I.w_lens : nullptr;
+    b.d_mode = const_cast<uint8_t *>(d_blob) + I.mode_off;
+    b.d_bits = (uint32_t *)(const_cast<uint8_t *>(d_blob) + I.bits_off);
+    b.d_pay_off = (uint64_t *)(w + I.w_pay_off);
+    b.d_payload = const_cast<uint8_t *>(d_blob) + I.payload_off;
+    b.payload_cap = I.pay_total;
+    b.d_sync_off = (uint64_t *)(w + I.w_sync_off);
+    b.d_sync_len = (uint16_t *)(const_cast<uint8_t *>(d_blob) + I.sync_off);
+    b.sync_cap = I.sync_total;
+    b.d_status = (int32_t *)(w + I.w_status);
+    view->d_seg_off = (uint64_t *)(w + I.w_seg_off);
+    view->d_cstatus = (int32_t *)(w + I.w_cstatus);
+    view->d_tid = I.tid_off ? d_blob + I.tid_off : nullptr;
+    view->d_crc = I.crc_off ? (const uint32_t *)(d_blob + I.crc_off) : nullptr;
+    view->d_set = I.kind == DC_BB_KIND_SET ? d_blob + I.rec_off : nullptr;
+    view->K = I.K;
+    view->d_table = I.kind == DC_BB_KIND_SHARED ? (const dc_dtable *)(w + I.w_table) : nullptr;
+    view->total_bytes = I.total_bytes;
+    unsigned long long *first;
+    if (const int r = hbatch_begin(c, 0, &first)) return r;
+    if (n) {
+        LAUNCH(c, "hbb_open_seg", k_hbb_open_seg, hbatch_grid(c, (n + HB_THREADS - 1) / HB_THREADS, 2048), HB_THREADS, d_blob, I,
+               items, b.d_status, first);
+        LAUNCH(c, "hbb_scan_seg", k_scan_u64, 1, 1024, (const uint64_t *)items, n, view->d_seg_off);
+        LAUNCH(c, "hbb_scan_pay", k_scan_u64, 1, 1024, (const uint64_t *)(items + n), n, b.d_pay_off);
+        LAUNCH(c, "hbb_scan_sync", k_scan_u64, 1, 1024, (const uint64_t *)(items + 2 * n), n, b.d_sync_off);
+    } else {
+        HIPCHK(hipMemsetAsync(view->d_seg_off, 0, sizeof(uint64_t), c->stream));
+        HIPCHK(hipMemsetAsync(b.d_pay_off, 0, sizeof(uint64_t), c->stream));
+        HIPCHK(hipMemsetAsync(b.d_sync_off, 0, sizeof(uint64_t), c->stream));
+    }
+    LAUNCH(c, "hbb_open_end", k_hbb_open_end, 1, 64, I, (const uint64_t *)view->d_seg_off, (const uint64_t *)b.d_pay_off,
+           (const uint64_t *)b.d_sync_off, view->d_cstatus);
+    if (I.kind == DC_BB_KIND_OWN4 && n)
+        LAUNCH(c, "hb_lens_unpack", k_hb_lens_unpack, hbatch_grid(c, (n + HBL_RECS - 1) / HBL_RECS, 2048), HB_THREADS,
+               d_blob + I.rec_off, n, b.d_lens);
+    if (I.kind == DC_BB_KIND_SHARED) {
+        int32_t *const lengths = (int32_t *)(w + I.w_lengths);
+        LAUNCH(c, "hbb_widen", k_hbb_widen, 1, HB_THREADS, d_blob + I.rec_off, lengths);
+        return dc_huff_table_lengths(c, lengths, 258, I.n_ary, (dc_dtable *)(w + I.w_table));
+    }
     return DC_OK;
 }
 

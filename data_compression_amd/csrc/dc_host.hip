@@ -803,4 +803,158 @@ int dc_small_compress_host(const uint8_t *in, uint64_t n, uint8_t *out, uint64_t
 int dc_small_decompress_host(const uint8_t *in, uint64_t m, uint8_t *out, uint64_t cap, uint64_t *len)
 { return run_bytes(3, in, m, 0, out, cap, len); }
 
+// ---- many small host buffers <-> one DCHB container (dc_gpu.h "container DCHB") ---------------
+// one allocation, carved into arrays that each start at a multiple of 256
+struct Carve {
+    uint8_t *base;
+    uint64_t at;
+    uint64_t take(uint64_t bytes)
+    {
+        const uint64_t o = at;
+        at += (bytes + 255) & ~255ull;
+        return o;
+    }
+};
+
+// the shared table of the whole input (its histogram, capped at max_digits when that is not 0),
+// or the one of 256 given lengths, in s->table
+static int batch_host_table(HostState *s, const uint8_t *d_in, uint64_t total, int n_ary, int max_digits,
+                            const uint8_t *lengths256, dc_dtable **d_tab)
+{
+    RC(s->table.need(dc_dtable_size()));
+    *d_tab = (dc_dtable *)s->table.p;
+    if (lengths256) {
+        int32_t L[259];
+        for (int k = 0; k < 259; ++k) L[k] = k < 256 ? lengths256[k] : 0;
+        RC(s->lens.need(sizeof(L)));
+        RC(dc_memcpy_h2d(s->ctx, s->lens.p, L, sizeof(L)));
+        return dc_huff_table_lengths(s->ctx, (const int32_t *)s->lens.p, 258, n_ary, *d_tab);
+    }
+    RC(s->hist.need(256 * sizeof(uint64_t)));
+    uint64_t *const d_hist = (uint64_t *)s->hist.p;
+    if (total) RC(dc_huff_hist(s->ctx, d_in, total, d_hist));
+    else RC(dc_memset(s->ctx, d_hist, 0, 256 * sizeof(uint64_t)));
+    return max_digits ? dc_huff_table_limit(s->ctx, d_hist, 258, n_ary, max_digits, *d_tab)
+                      : dc_huff_table(s->ctx, d_hist, 258, n_ary, *d_tab);
+}
+
+int dc_huff_batch_compress_host(const uint8_t *in, const uint64_t *h_off, uint64_t count, int n_ary, uint32_t sync_syms,
+                                int kind, int flags, int max_digits, const uint8_t *lengths_or_set, uint32_t K,
+                                uint8_t *out, uint64_t cap, uint64_t *out_len)
+{
+    if (!h_off || !out_len || (cap && !out) || max_digits < 0 || n_ary < 2 || n_ary > 256) return DC_E_ARG;
+    for (uint64_t i = 0; i < count; ++i)
+        if (h_off[i + 1] < h_off[i]) return DC_E_ARG;
+    const uint64_t total = h_off[count];
+    if (total && !in) return DC_E_ARG;
+    const bool own = kind == 0 || kind == 1;
+    if (own) K = 0;
+    else if (!lengths_or_set || kind == 2) K = 1;
+    dc_hblob_info I;
+    RC(dc_huff_batch_blob_layout(count, kind, flags, K, &I));
+    const uint64_t bound = dc_huff_batch_blob_bound(total, count, sync_syms, kind, flags, K);
+    if (!bound) return DC_E_ARG;
+    HostState *s;
+    RC(state(&s));
+    const uint8_t *d_in = nullptr;
+    RC(dc_host_upload(in, total, &d_in));
+    RC(s->out.need(bound));
+    uint8_t *const d_blob = (uint8_t *)s->out.p;
+    const uint64_t sync_cap = dc_huff_batch_sync_bound(total, count, sync_syms);
+    Carve C{nullptr, 0};
+    const uint64_t o_off = C.take(8 * (count + 1)), o_lens = C.take(own ? 256 * count : 0), o_mode = C.take(count),
+                   o_bits = C.take(4 * count), o_po = C.take(8 * (count + 1)), o_so = C.take(8 * (count + 1)),
+                   o_sync = C.take(2 * sync_cap), o_st = C.take(4 * count), o_sst = C.take(4 * count),
+                   o_tid = C.take(count), o_crc = C.take(4 * count), o_cst = C.take(4 * count), o_info = C.take(16),
+                   o_set = C.take(256ull * (K ? K : 1));
+    RC(s->aux.need(C.at));
+    uint8_t *const w = (uint8_t *)s->aux.p;
+    uint64_t *const d_off = (uint64_t *)(w + o_off);
+    RC(dc_memcpy_h2d(s->ctx, d_off, h_off, 8 * (count + 1)));
+    dc_hbatch b;
+    memset(&b, 0, sizeof(b));
+    b.count = count;
+    b.n_ary = n_ary;
+    b.sync_syms = sync_syms;
+    b.d_lens = own ? w + o_lens : nullptr;
+    b.d_mode = w + o_mode;
+    b.d_bits = (uint32_t *)(w + o_bits);
+    b.d_pay_off = (uint64_t *)(w + o_po);
+    b.d_payload = d_blob + I.payload_off;   // in place: the seal copies the sync index alone
+    b.payload_cap = dc_huff_batch_payload_bound(total, count);
+    b.d_sync_off = (uint64_t *)(w + o_so);
+    b.d_sync_len = (uint16_t *)(w + o_sync);
+    b.sync_cap = sync_cap;
+    b.d_status = (int32_t *)(w + o_st);
+    uint8_t *const d_tid = w + o_tid, *const d_set = w + o_set;
+    uint32_t *const d_crc = (uint32_t *)(w + o_crc);
+    const void *tables = nullptr;
+    if (own) {
+        RC(dc_huff_encode_batch_limit(s->ctx, d_in, d_off, count, max_digits, &b));
+    } else {
+        dc_dtable *d_tab = nullptr;
+        if (kind == 2 || !lengths_or_set) RC(batch_host_table(s, d_in, total, n_ary, max_digits, lengths_or_set, &d_tab));
+        if (kind == 2) {
+            tables = d_tab;
+            RC(dc_huff_encode_batch_shared(s->ctx, d_in, d_off, count, d_tab, &b));
+        } else {
+            uint8_t rec[256];
+            if (!lengths_or_set) {   // a set of the one record of the table built above
+                int32_t L[DC_MAX_SYMS];
+                int got = 0;
+                RC(dc_huff_table_get_lengths(s->ctx, d_tab, L, DC_MAX_SYMS, &got));
+                for (int k = 0; k < 256; ++k) rec[k] = k < got && L[k] > 0 && L[k] < 256 ? (uint8_t)L[k] : 0;
+            }
+            RC(dc_memcpy_h2d(s->ctx, d_set, lengths_or_set ? lengths_or_set : rec, 256ull * K));
+            tables = d_set;
+            RC(dc_huff_encode_batch_set(s->ctx, d_in, d_off, count, d_set, K, d_tid, &b));
+        }
+    }
+    if ((flags & 1) && count)
+        RC(dc_crc32_batch(s->ctx, d_in, total, d_off, d_off + 1, count, d_crc, (int32_t *)(w + o_cst)));
+    uint64_t *const d_info = (uint64_t *)(w + o_info);
+    RC(dc_huff_batch_seal(s->ctx, &b, d_off, kind, flags, tables, K, d_tid, d_crc, d_blob, bound, d_info,
+                          (int32_t *)(w + o_sst)));
+    uint64_t info[2] = {0, 0};
+    RC(dc_memcpy_d2h(s->ctx, info, d_info, sizeof(info)));   // (synchronising)
+    if (info[1]) return (int)(int64_t)info[1];
+    if (const int st = dc_huff_batch_status(s->ctx)) return st;   // the seal's slot carries the encode's failures
+    if (info[0] > cap) return DC_E_CAPACITY;
+    RC(dc_memcpy_d2h(s->ctx, out, d_blob, info[0]));
+    *out_len = info[0];
+    return DC_OK;
+}
+
+int dc_huff_batch_decompress_host(const uint8_t *blob, uint64_t m, uint8_t *out, uint64_t cap, uint64_t *h_off_out,
+                                  uint64_t *count)
+{
+    if (!blob || !count || (cap && !out)) return DC_E_ARG;
+    RC(dc_huff_batch_blob_check(blob, m));   // before the first device call
+    dc_hblob_info I;
+    RC(dc_huff_batch_blob_info(blob, m, &I));
+    *count = I.count;
+    if (I.total_bytes > cap) return DC_E_CAPACITY;
+    HostState *s;
+    RC(state(&s));
+    const uint8_t *d_blob = nullptr;
+    RC(dc_host_upload(blob, I.blob_bytes, &d_blob));
+    RC(s->aux.need(I.work_bytes));
+    RC(s->out.need(I.total_bytes + 64));
+    uint8_t *const d_out = (uint8_t *)s->out.p;
+    dc_hblob_view v;
+    RC(dc_huff_batch_open(s->ctx, d_blob, I.blob_bytes, &I, s->aux.p, I.work_bytes, &v));
+    if (I.kind == 2) RC(dc_huff_decode_batch_shared(s->ctx, &v.batch, v.d_table, d_out, v.d_seg_off, I.total_bytes));
+    else if (I.kind == 3) RC(dc_huff_decode_batch_set(s->ctx, &v.batch, v.d_set, v.K, v.d_tid, d_out, v.d_seg_off, I.total_bytes));
+    else RC(dc_huff_decode_batch(s->ctx, &v.batch, d_out, v.d_seg_off, I.total_bytes));
+    if (v.d_crc && I.count)
+        RC(dc_crc32_verify_batch(s->ctx, d_out, I.total_bytes, v.d_seg_off, v.d_seg_off + 1, I.count, v.d_crc, v.batch.d_status));
+    if (const int st = dc_huff_batch_status(s->ctx)) return st;   // (synchronising)
+    RC(dc_memcpy_d2h(s->ctx, out, d_out, I.total_bytes));
+    if (h_off_out) {
+        if (I.count) RC(dc_memcpy_d2h(s->ctx, h_off_out, v.d_seg_off, 8 * (I.count + 1)));
+        else h_off_out[0] = 0;
+    }
+    return DC_OK;
+}
+
 }  // extern "C"

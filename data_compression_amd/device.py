@@ -1054,6 +1054,165 @@ class Codec:
         synchronising."""
         return int(self.L.dc_huff_batch_status(self.ctx))
 
+    # ---- the storable form of a batch (dc_gpu.h "Huffman batch v1: container DCHB") ---------------
+    BLOB_OWN, BLOB_OWN4, BLOB_SHARED, BLOB_SET = 0, 1, 2, 3   # the header's kind
+    BLOB_CRC = 1                                              # flag bit 0
+
+    @staticmethod
+    def _blob_kind(enc, lens4: bool = False):
+        """(kind, flags, K, tables) of the dict encode_batch returned."""
+        flags = Codec.BLOB_CRC if enc.get("crc") is not None else 0
+        if enc.get("table_set") is not None:
+            return Codec.BLOB_SET, flags, int(enc["table_set"].shape[0]), enc["table_set"]
+        if enc.get("table") is not None:
+            return Codec.BLOB_SHARED, flags, 1, enc["table"]
+        return (Codec.BLOB_OWN4 if lens4 else Codec.BLOB_OWN), flags, 0, None
+
+    def batch_blob_bound(self, total_bytes: int, count: int, sync_syms: int, kind: int = 0, flags: int = 0, K: int = 0) -> int:
+        """dc_huff_batch_blob_bound: bytes that always hold a sealed batch. ValueError for
+        arguments the format does not take."""
+        b = int(self.L.dc_huff_batch_blob_bound(total_bytes, count, sync_syms, kind, flags, K))
+        if b == 0:
+            raise ValueError("batch_blob_bound: count, sync_syms, kind, flags or K outside the DCHB format")
+        return b
+
+    def batch_blob_layout(self, count: int, kind: int = 0, flags: int = 0, K: int = 0) -> dict:
+        """dc_huff_batch_blob_layout: the section offsets the host knows before an encode
+        (payload_off among them), as a dict of ints."""
+        from ._lib import HBlobInfo
+        info = HBlobInfo()
+        check("dc_huff_batch_blob_layout", self.L.dc_huff_batch_blob_layout(count, kind, flags, K, C.byref(info)))
+        return info.as_dict()
+
+    def batch_seal(self, enc, out=None, lens4: bool = False):
+        """dc_huff_batch_seal of the dict encode_batch returned: (blob, info, status). blob: a
+        uint8 device tensor (out, or a new one of batch_blob_bound bytes) whose first info[0]
+        bytes are the container; info: an int64 device tensor, (blob_bytes, container status: 0,
+        DC_E_CAPACITY when out is too small, DC_E_ARG for a shared table that cannot be stored);
+        status: int32 per segment (the encode's for a segment it failed, which is sealed empty;
+        DC_E_CODE_TOO_LONG for a record that has no nybble form). The kind (own tables, shared
+        table, table set), tid, crc and the table or set are taken from enc; lens4: own tables as
+        128-byte nybble records. The payload is not copied when enc["payload"] already lies at
+        out[payload_off:] (encode_batch_blob). Asynchronous, no host read."""
+        kind, flags, K, tables = self._blob_kind(enc, lens4)
+        count = enc["count"]
+        if out is None:
+            out = self._t(self.batch_blob_bound(enc["total"], count, enc["S"], kind, flags, K))
+        if out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous() or out.data_ptr() & 15:
+            raise ValueError("batch_seal out: a contiguous, 16-B aligned uint8 device tensor")
+        info = self._t(2, torch.int64)
+        status = self._t(max(count, 1), torch.int32)[:count]
+        b = self._hbatch(enc, enc["payload_cap"], enc["sync_cap"])
+        check("dc_huff_batch_seal",
+              self.L.dc_huff_batch_seal(self.ctx, C.byref(b), _ptr(enc["offsets"]), kind, flags, _ptr(tables), K,
+                                        _ptr(enc.get("tid")), _ptr(enc.get("crc")), _ptr(out), out.numel(), _ptr(info),
+                                        _ptr(status)))
+        return out, info, status
+
+    def encode_batch_blob(self, x, offsets, lens4: bool = False, **kw):
+        """encode_batch(x, offsets, **kw) straight into a container: the blob is allocated at its
+        bound, the encoder writes the payload at blob[payload_off:] (the offsets up to there depend
+        on count and the mode alone), and batch_seal adds the directory, the sync index and the
+        header: the payload is never copied. Returns batch_seal's (blob, info, status).
+        Asynchronous, no host read."""
+        offsets = self._i64(offsets, range(1, 1 << 62), "encode_batch_blob offsets")
+        count = offsets.numel() - 1
+        ts = kw.get("table_set")
+        kind = self.BLOB_SET if ts is not None else self.BLOB_SHARED if kw.get("table") is not None else \
+            self.BLOB_OWN4 if lens4 else self.BLOB_OWN
+        flags = self.BLOB_CRC if kw.get("checksum") else 0
+        K = int(ts.shape[0]) if kind == self.BLOB_SET else 1 if kind == self.BLOB_SHARED else 0
+        S = kw.get("sync_syms", 64)
+        blob = self._t(self.batch_blob_bound(x.numel(), count, S, kind, flags, K))
+        at = self.batch_blob_layout(count, kind, flags, K)["payload_off"]
+        pb = self.batch_bounds(x.numel(), count, S)[0]
+        if flags and count and x.numel() == 0:
+            # an input of no bytes has no address for crc32_batch to take; every segment it can hold
+            # is empty, and the CRC-32 of no bytes is 0
+            enc = self.encode_batch(x, offsets, payload=blob[at: at + pb], **dict(kw, checksum=False))
+            enc["crc"] = self._t(count, torch.int32).zero_().view(torch.uint32)
+        else:
+            enc = self.encode_batch(x, offsets, payload=blob[at: at + pb], **kw)
+        return self.batch_seal(enc, out=blob, lens4=lens4)
+
+    def batch_info(self, blob) -> dict:
+        """dc_huff_batch_blob_info of a container (device tensor, bytes or numpy): the header's
+        fields and the section offsets as a dict of ints; a device tensor costs one 64-byte copy.
+        DcError (DC_E_STREAM) for a header that breaks the rule of the format."""
+        from ._lib import HBlobInfo
+        if hasattr(blob, "data_ptr"):
+            head, m = blob[:64].cpu().numpy().tobytes(), blob.numel()
+        else:
+            blob = np.frombuffer(blob, np.uint8) if isinstance(blob, (bytes, bytearray, memoryview)) else \
+                np.ascontiguousarray(blob, np.uint8).reshape(-1)
+            head, m = blob[:64].tobytes(), blob.size
+        info = HBlobInfo()
+        buf = C.create_string_buffer(head, 64)
+        check("dc_huff_batch_blob_info", self.L.dc_huff_batch_blob_info(C.cast(buf, C.c_void_p), m, C.byref(info)))
+        return info.as_dict()
+
+    def batch_open(self, blob):
+        """dc_huff_batch_open: a container (a uint8 device tensor, or bytes / numpy, which are
+        uploaded) as a dict that decode_batch, decode_batch_ranges and decode_batch(verify=True)
+        accept as they accept encode_batch's: mode, bits, payload, sync_len (and lens of kind 0,
+        tid and table_set of kind 3, crc) are views into the blob; pay_off, sync_off, offsets,
+        status (and kind 1's unpacked lens, kind 2's rebuilt table) lie in one workspace tensor.
+        Also "total", "info" (batch_info's dict) and "container_status" (an int32 device tensor of
+        one entry: 0, or DC_E_STREAM when the directory's scans do not end at the header's totals;
+        "status" has DC_E_STREAM for each segment that breaks its own rule). DcError (DC_E_STREAM)
+        for a header that breaks the rule. One 64-byte read of a device blob, then asynchronous."""
+        from ._lib import HBlobInfo, HBlobView
+        if not hasattr(blob, "data_ptr"):
+            host = np.frombuffer(blob, np.uint8) if isinstance(blob, (bytes, bytearray, memoryview)) else \
+                np.ascontiguousarray(blob, np.uint8).reshape(-1)
+            dev = self._t(max(host.size, 1))[: host.size]
+            dev.copy_(torch.from_numpy(host.copy()))
+            head, blob = host[:64].tobytes(), dev
+        else:
+            if blob.dtype != torch.uint8 or not blob.is_cuda or not blob.is_contiguous():
+                raise ValueError("batch_open: a contiguous uint8 device tensor, bytes or numpy")
+            if blob.data_ptr() & 15:
+                blob = blob.clone()
+            head = blob[:64].cpu().numpy().tobytes()
+        m = blob.numel()
+        info = HBlobInfo()
+        hbuf = C.create_string_buffer(head, 64)
+        check("dc_huff_batch_blob_info", self.L.dc_huff_batch_blob_info(C.cast(hbuf, C.c_void_p), m, C.byref(info)))
+        I = info.as_dict()
+        work = self._t(max(I["work_bytes"], 256))
+        view = HBlobView()
+        check("dc_huff_batch_open",
+              self.L.dc_huff_batch_open(self.ctx, _ptr(blob), m, C.byref(info), _ptr(work), work.numel(), C.byref(view)))
+        n, kind = I["count"], I["kind"]
+
+        def part(t, off, nbytes, dtype=None):
+            v = t[off: off + nbytes]
+            return v if dtype is None else v.view(dtype)
+
+        enc = {"count": n, "n_ary": I["n_ary"], "S": I["sync_syms"], "total": I["total_bytes"], "max_bits": None,
+               "offsets": part(work, I["w_seg_off"], 8 * (n + 1), torch.int64),
+               "mode": part(blob, I["mode_off"], n), "bits": part(blob, I["bits_off"], 4 * n, torch.int32),
+               "pay_off": part(work, I["w_pay_off"], 8 * (n + 1), torch.int64),
+               "payload": part(blob, I["payload_off"], I["pay_total"]),
+               "sync_off": part(work, I["w_sync_off"], 8 * (n + 1), torch.int64),
+               "sync_len": part(blob, I["sync_off"], 2 * I["sync_total"], torch.int16),
+               "status": part(work, I["w_status"], 4 * n, torch.int32),
+               "container_status": part(work, I["w_cstatus"], 4, torch.int32),
+               "payload_cap": I["pay_total"], "sync_cap": I["sync_total"], "lens": None,
+               "info": I, "blob": blob, "work": work}
+        if kind == self.BLOB_OWN:
+            enc["lens"] = part(blob, I["rec_off"], 256 * n).view(n, 256)
+        elif kind == self.BLOB_OWN4:
+            enc["lens"] = part(work, I["w_lens"], 256 * n).view(n, 256)
+        elif kind == self.BLOB_SHARED:
+            enc["table"] = part(work, I["w_table"], self.table_bytes)
+        else:
+            enc["table_set"] = part(blob, I["rec_off"], 256 * I["K"]).view(I["K"], 256)
+            enc["tid"] = part(blob, I["tid_off"], n)
+        if I["flags"] & self.BLOB_CRC:
+            enc["crc"] = part(blob, I["crc_off"], 4 * n, torch.uint32)
+        return enc
+
     # ---- checksums: CRC-32 per buffer (dc_gpu.h "checksums") -----------------------------------
     CRC_TILE = 1024       # DC_CRC_TILE: the bytes a wave takes at a time
     CRC_PIECE = 131072    # DC_CRC_PIECE: dc_crc32's bytes per wave

@@ -166,6 +166,88 @@ def decompress_range(blob: bytes, first: int, count: int) -> bytes:
     return bytes(out[: got.value])
 
 
+def compress_batch(buffers, n_ary: int = 2, sync_syms: int = 64, mode: str = "own", max_bits=None, checksum: bool = True,
+                   lens4: bool = False, k: int = 4) -> bytes:
+    """Many small buffers (each at most 65536 bytes) into one "DCHB" container (dc_gpu.h
+    "container DCHB"), by dc_huff_batch_compress_host: what to write to a file.
+    mode "own": a table per buffer; max_bits caps them. lens4 stores them as 128-byte nybble
+    records, which hold lengths up to 15: max_bits then defaults to 15, and a larger one raises
+    DcError (DC_E_CODE_TOO_LONG) for a buffer whose table is deeper.
+    mode "shared": one table, built on the device from all the bytes (capped at max_bits).
+    mode "set": k tables trained on the buffers (Codec.batch_table_set; max_bits 12 by default).
+    checksum: a CRC-32 per buffer is stored, and verified by decompress_batch.
+    A buffer that cannot be encoded raises DcError with its status."""
+    from .device import Codec
+    if mode not in ("own", "shared", "set"):
+        raise ValueError("compress_batch mode: own, shared or set")
+    bufs = [bytes(b) for b in buffers]
+    data = b"".join(bufs)
+    off = np.concatenate(([0], np.cumsum([len(b) for b in bufs]))).astype(np.uint64)
+    kind = {"own": 1 if lens4 else 0, "shared": 2, "set": 3}[mode]
+    if kind == 1 and max_bits is None:
+        max_bits = 15
+    records, K = None, 0
+    if mode == "set":
+        import torch
+        c = Codec()
+        try:
+            x = torch.from_numpy(np.frombuffer(data, np.uint8).copy()).to(f"cuda:{c.device}")
+            ts = c.batch_table_set(x, off.astype(np.int64), k, n_ary, **({} if max_bits is None else {"max_bits": max_bits}))
+            records = np.ascontiguousarray(ts.cpu().numpy(), np.uint8)
+        finally:
+            c.close()
+        K = records.shape[0]
+    cap = int(core().dc_huff_batch_blob_bound(len(data), len(bufs), sync_syms, kind, int(bool(checksum)), K or (kind == 2)))
+    if cap == 0:
+        raise ValueError("compress_batch: sync_syms or the number of buffers is outside the DCHB format")
+    out = (C.c_uint8 * cap)()
+    got = C.c_uint64(0)
+    src = (C.c_uint8 * max(len(data), 1)).from_buffer_copy(data + b"\0")
+    rc = core().dc_huff_batch_compress_host(
+        src, off.ctypes.data_as(C.POINTER(C.c_uint64)), len(bufs), n_ary, sync_syms, kind, int(bool(checksum)),
+        Codec.max_digits(n_ary, max_bits), None if records is None else records.ctypes.data_as(C.POINTER(C.c_uint8)), K,
+        out, cap, C.byref(got))
+    if rc:
+        raise DcError("dc_huff_batch_compress_host", rc)
+    return bytes(out[: got.value])
+
+
+def batch_info(blob) -> dict:
+    """dc_huff_batch_blob_check, then dc_huff_batch_blob_info, of a container in host memory
+    (pure host, no device): the header's fields and section offsets. DcError (DC_E_STREAM) for a
+    blob that breaks the container rule."""
+    from ._lib import HBlobInfo
+    blob = bytes(blob)
+    buf = C.cast(C.c_char_p(blob), C.c_void_p)
+    rc = core().dc_huff_batch_blob_check(buf, len(blob))
+    if rc:
+        raise DcError("dc_huff_batch_blob_check", rc)
+    info = HBlobInfo()
+    rc = core().dc_huff_batch_blob_info(buf, len(blob), C.byref(info))
+    if rc:
+        raise DcError("dc_huff_batch_blob_info", rc)
+    return info.as_dict()
+
+
+def decompress_batch(blob) -> list:
+    """The buffers of a "DCHB" container, as a list of bytes, by dc_huff_batch_decompress_host:
+    the container rule is checked on the host before the first device call; stored CRCs are
+    verified. DcError with the status of the first failing buffer (DC_E_STREAM, DC_E_CHECKSUM)
+    when one does not decode."""
+    blob = bytes(blob)
+    info = batch_info(blob)
+    n, total = info["count"], info["total_bytes"]
+    out = (C.c_uint8 * max(total, 1))()
+    off = (C.c_uint64 * (n + 1))()
+    count = C.c_uint64(0)
+    src = C.cast(C.c_char_p(blob), C.POINTER(C.c_uint8))
+    rc = core().dc_huff_batch_decompress_host(src, len(blob), out, total, off, C.byref(count))
+    if rc:
+        raise DcError("dc_huff_batch_decompress_host", rc)
+    data = bytes(out[:total])
+    return [data[off[i]: off[i + 1]] for i in range(n)]
+
+
 def histogram_bytes(data: bytes, max_symbol_value: int = 258) -> np.ndarray:
     """Histogram of an arbitrary byte string (NULs included), via the device API."""
     from .device import Codec

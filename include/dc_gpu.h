@@ -701,6 +701,132 @@ int dc_huff_decode_batch_set_ranges(dc_ctx *ctx, const dc_hbatch *batch, const u
  * launch, no host read. DC_E_ARG for K outside 1..DC_BATCH_SET_MAX or a NULL pointer. */
 int dc_huff_batch_set_hist(dc_ctx *ctx, const uint8_t *d_in, const uint64_t *d_in_off, uint64_t count,
                            const uint8_t *d_tid, uint32_t K, uint64_t *d_hist);
+/* ---- Huffman batch v1: container DCHB ---------------------------------------------------------
+ * The form of a batch that can be written to a file and read back (the reference asks for a
+ * version number "in the header of the output file / stream", n_ary_huffman.c:211-232, a reader
+ * that fails politely on foreign or future files, :1944-1973, and blocks that carry their own
+ * decompressed length "so a parallel processor can skip ahead", small_compression.c:924-926). One
+ * blob holds everything a decode needs; pay_off, sync_off and the segment offsets are not stored:
+ * they are the exclusive scans of round_up_16(ceil(bits / 8)), ceil(len / S) and len, which open
+ * derives with the scan kernel the encoder uses. Per segment the blob stores len, bits and mode,
+ * 9 bytes (10 with a tid, 13 or 14 with a CRC).
+ * Format "DCHB" version 1. Little-endian. Every section starts at a multiple of 16 bytes from
+ * the start of the blob; gap bytes are zero. The blob must be 16-B aligned on the device, which
+ * gives the payload the alignment the decoders require.
+ *   header, 64 bytes:
+ *      0  u32 magic "DCHB"             4  u8 version = 1
+ *      5  u8 kind: 0 own tables, 256-byte records; 1 own tables, 128-byte nybble records (the
+ *         layout of dc_huff_batch_lens_pack); 2 one shared table; 3 table set
+ *      6  u8 flags: bit 0 = a CRC-32 per segment is stored; every other bit 0
+ *      7  u8 K, records in the record section: 0 for kinds 0 and 1, 1 for kind 2,
+ *         1..DC_BATCH_SET_MAX for kind 3
+ *      8  u16 n_ary (2..256)          10  u16 sync_syms (a power of two, 16..DC_SYNC_MAX)
+ *     12  u32 0                       16  u64 count (at most DC_RANGES_MAX)
+ *     24  u64 total_bytes = sum of len
+ *     32  u64 sync_total (u16 entries) 40  u64 pay_total (bytes, a multiple of 16)
+ *     48  u64 blob_bytes (the whole container)
+ *     56  u32 0                       60  u32 CRC-32 (dc_crc32_host) of header bytes 0..59
+ *   sections, in this order: len u32[count]; bits u32[count]; mode u8[count]; tid u8[count]
+ *   (kind 3 only); crc u32[count] (flag bit 0 only); records: u8[256 count] for kind 0,
+ *   u8[128 count] for kind 1, u8[256 K] for kinds 2 and 3; payload u8[pay_total], the batch's
+ *   d_payload[0 .. pay_off[count]) verbatim, 16-B pads included; sync u16[sync_total], the batch's
+ *   d_sync_len[0 .. sync_off[count]) verbatim.
+ *   The offsets of every section up to the payload depend on count, kind, flags and K alone
+ *   (dc_huff_batch_blob_layout), so a caller can have the encoder write the payload in place; only
+ *   the sync section, at payload_off + pay_total, and blob_bytes depend on device values.
+ *   The record of kind 2 holds the shared table's lengths in digits for bytes 0..255.
+ * The container rule (csrc/dc_batch_blob.h; what dc_huff_batch_blob_check enforces on the host and
+ * dc_huff_batch_blob_info plus dc_huff_batch_open on the device): the header as above, reserved
+ * fields zero, the header CRC; len[i] <= DC_BATCH_SEG_MAX; mode[i] <= 1; bits[i] <= 8 len[i] with
+ * equality when mode is 0; tid[i] < K for a mode-1 segment of kind 3; the three scans end at
+ * total_bytes, pay_total and sync_total; blob_bytes is the sum of the padded sections and at most
+ * the m bytes given, with no arithmetic that can wrap. Gap bytes, payload pads, records, payload
+ * bytes, sync entries and CRCs are NOT inspected by the rule: the decoders hold records, payload
+ * and sync entries to their own tests (DC_E_STREAM per segment), and decode with verify the CRCs.
+ * dc_hblob_info: the header's fields, the section offsets (0: the section is absent), and the
+ * bytes and offsets of open's workspace. */
+typedef struct dc_hblob_info {
+    uint32_t version, kind, flags, K;
+    int32_t n_ary;
+    uint32_t sync_syms;
+    uint64_t count, total_bytes, sync_total, pay_total, blob_bytes;
+    uint64_t len_off, bits_off, mode_off, tid_off, crc_off, rec_off, rec_bytes, payload_off, sync_off;
+    uint64_t work_bytes;
+    uint64_t w_items, w_pay_off, w_sync_off, w_seg_off, w_status, w_cstatus, w_lens, w_lengths, w_table;
+} dc_hblob_info;
+/* Pure host (csrc/dc_batch_blob.h). bound: bytes that always hold a seal, the host sections plus
+ * round_up_16(dc_huff_batch_payload_bound) and the padded dc_huff_batch_sync_bound entries; 0 for
+ * arguments that are not legal or a bound past 2^64. layout: the host-known fields of *info
+ * (count, kind, flags, K, the offsets up to payload_off, the workspace) or DC_E_ARG. info: the
+ * header rule on the 64 header bytes of a container of which m bytes exist, then every field of
+ * *info; DC_E_STREAM for a header that breaks it. check: the whole container rule on a blob in
+ * host memory, DC_OK or DC_E_STREAM. */
+uint64_t dc_huff_batch_blob_bound(uint64_t total_bytes, uint64_t count, uint32_t sync_syms, int kind, int flags,
+                                  uint32_t K);
+int dc_huff_batch_blob_layout(uint64_t count, int kind, int flags, uint32_t K, dc_hblob_info *info);
+int dc_huff_batch_blob_info(const uint8_t *header64, uint64_t m, dc_hblob_info *info);
+int dc_huff_batch_blob_check(const uint8_t *blob, uint64_t m);
+/* Seal an encoded batch into d_blob (blob_cap bytes, 16-B aligned). d_in_off: the encode's.
+ * tables: NULL for kinds 0 and 1 (batch->d_lens is read), the dc_dtable for kind 2, the set (16-B
+ * aligned) for kind 3; d_tid for kind 3, d_crc (u32[count], dc_crc32_batch) with flag bit 0.
+ * Asynchronous, no host read, launches that do not depend on count; count 0 seals a valid
+ * 64-byte container. d_info (device u64[2]) receives blob_bytes and the container status:
+ *   DC_OK          the container is complete
+ *   DC_E_CAPACITY  blob_bytes would pass blob_cap: no byte at or past the cap is written, and no
+ *                  header (sections that end below the cap may have been written). When even
+ *                  the host-known sections do not fit (payload_off > blob_cap) nothing at all
+ *                  is written into the blob, and d_status and the first-failure slot are NOT
+ *                  written either: d_info alone answers for such a call
+ *   DC_E_ARG       kind 2: the table is of another arity, is no usable table, or has a code for a
+ *                  symbol at or above 256; any kind: a segment the encode failed with payload
+ *                  bytes or sync entries to its name (DC_E_CAPACITY at encode). No header.
+ * d_status[i] (i32): DC_OK; or the encode's status for a segment with batch->d_status[i] != DC_OK,
+ * which is sealed as an empty stored segment (len 0, bits 0, mode 0: what the encoder gave it, 0
+ * payload bytes and 0 sync entries); or DC_E_CODE_TOO_LONG for a kind 1 record with a length
+ * above 15, written as zeros (dc_huff_batch_lens_pack's rule: a mode-1 segment under it decodes
+ * to DC_E_STREAM, never to a wrong byte). The lowest failing index goes to the first-failure slot.
+ * Kind 0 records are copied as they are, except that the record of a segment the encode failed
+ * (kinds 0 and 1) is written as zeros: the encode never wrote it, and a container is a function
+ * of what was encoded, not of what the buffer held before. The payload is not copied when batch->d_payload ==
+ * d_blob + payload_off (encoded in place); any other overlap of the blob with the batch's arrays,
+ * d_in_off, tables, d_tid, d_crc, d_info or d_status is DC_E_ARG from the host. The header is written last, by the device. */
+int dc_huff_batch_seal(dc_ctx *ctx, const dc_hbatch *batch, const uint64_t *d_in_off, int kind, int flags,
+                       const void *tables, uint32_t K, const uint8_t *d_tid, const uint32_t *d_crc, uint8_t *d_blob,
+                       uint64_t blob_cap, uint64_t *d_info, int32_t *d_status);
+/* Open a container that lies in device memory (16-B aligned, m bytes). *info: dc_huff_batch_blob_
+ * info of its 64 header bytes (the caller has them in host memory, or fetches them with one
+ * 64-byte copy); its offsets are checked again here against count, kind, flags, K, the totals and
+ * m (DC_E_ARG), so the caps below are section sizes whatever filled it. d_work: work_bytes >=
+ * info->work_bytes, 256-B aligned, not overlapping the blob. Asynchronous, no host read,
+ * launches that do not depend on count: one pass applies the per-segment rule and writes the
+ * items of three scans, three scans, one kernel applies the totals rule; kind 1 unpacks its
+ * records into d_work, kind 2 builds its table there (dc_huff_table_lengths).
+ * The view: batch (d_mode, d_bits, d_payload, d_sync_len point into the blob, payload_cap =
+ * pay_total, sync_cap = sync_total; d_pay_off, d_sync_off, d_status in d_work; d_lens in the blob
+ * for kind 0, in d_work for kind 1, NULL otherwise), d_seg_off (count + 1 u64: what the decode
+ * calls take as d_out_off and the range calls as d_seg_off), d_cstatus (one i32: DC_OK, or
+ * DC_E_STREAM when a scan does not end at its total), and what the decode calls of the kind take:
+ * d_tid, d_set and K (kind 3), d_table (kind 2), d_crc (flag bit 0). batch.d_status[i] is DC_OK
+ * or DC_E_STREAM for a segment that breaks its rule (the first-failure slot has the lowest);
+ * the next decode overwrites it.
+ * Safety: a decode of an opened container neither reads nor writes out of bounds whatever open
+ * reported, because every decode kernel holds each segment's offsets inside payload_cap and
+ * sync_cap and to exact agreement with bits and the asked length before its first access
+ * (hb_record_check), and those caps are the host-checked section sizes. The statuses only have
+ * to tell the truth. */
+typedef struct dc_hblob_view {
+    dc_hbatch batch;
+    uint64_t *d_seg_off;
+    int32_t *d_cstatus;
+    const uint8_t *d_tid;
+    const uint32_t *d_crc;
+    const uint8_t *d_set;
+    uint32_t K;
+    const dc_dtable *d_table;
+    uint64_t total_bytes;
+} dc_hblob_view;
+int dc_huff_batch_open(dc_ctx *ctx, const uint8_t *d_blob, uint64_t m, const dc_hblob_info *info, void *d_work,
+                       uint64_t work_bytes, dc_hblob_view *view);
 
 /* base64url text (6 bits per char, MSB-first) of bits [bit_base, bit_base+bits) */
 int dc_huff_base64url(dc_ctx *ctx, const uint32_t *d_words, uint64_t bit_base, uint64_t bits,

@@ -106,6 +106,31 @@ int dc_small_compress_host(const uint8_t *in, uint64_t n, uint8_t *out, uint64_t
 int dc_small_decompress_host(const uint8_t *in, uint64_t m, uint8_t *out, uint64_t cap,
                              uint64_t *len);
 
+/* ---- many small host buffers <-> one "DCHB" container (dc_gpu.h "container DCHB") ----------
+ * compress: buffer i is in[h_off[i] .. h_off[i + 1]) (count + 1 offsets that do not decrease,
+ * each buffer at most DC_BATCH_SEG_MAX bytes). The input is uploaded, encoded with the payload
+ * in place, sealed, and blob_bytes are copied back to out (cap bytes; dc_huff_batch_blob_bound
+ * always holds them); *out_len = blob_bytes. kind and flags are the header's (flag bit 0: a
+ * CRC-32 per buffer is computed and stored). max_digits: kinds 0 and 1 cap every buffer's own
+ * table (0: no cap; kind 1 stores nybble records, so give at most 15); with lengths_or_set ==
+ * NULL it also caps the table built here. lengths_or_set: kind 2, the 256 code lengths in digits
+ * of the shared table; kind 3, K records of 256 lengths; NULL for kinds 2 and 3 builds the shared
+ * table from the whole input (kind 3: a set of that one record, K is ignored); ignored for kinds
+ * 0 and 1. Returns DC_E_ARG for arguments the format does not take, DC_E_CAPACITY when cap is
+ * too small, and otherwise the status of the first buffer that failed (DC_E_ARG for one that is
+ * too long, DC_E_CODE_TOO_LONG for a kind 1 record deeper than 15): nothing is written then.
+ * decompress: dc_huff_batch_blob_check runs before the first device call (DC_E_STREAM); then the
+ * blob is uploaded, opened and decoded, stored CRCs are verified, and the first failing status
+ * is returned (DC_E_STREAM, DC_E_CHECKSUM), nothing copied. out receives total_bytes bytes
+ * (DC_E_CAPACITY when cap is smaller), h_off_out (may be NULL) the count + 1 offsets of the
+ * buffers in out, *count their number: dc_huff_batch_blob_info sizes both beforehand. */
+int dc_huff_batch_compress_host(const uint8_t *in, const uint64_t *h_off, uint64_t count, int n_ary,
+                                uint32_t sync_syms, int kind, int flags, int max_digits,
+                                const uint8_t *lengths_or_set, uint32_t K, uint8_t *out, uint64_t cap,
+                                uint64_t *out_len);
+int dc_huff_batch_decompress_host(const uint8_t *blob, uint64_t m, uint8_t *out, uint64_t cap,
+                                  uint64_t *h_off_out, uint64_t *count);
+
 #ifdef __cplusplus
 }
 #endif
